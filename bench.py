@@ -20,6 +20,12 @@ some of the time without a trained checkpoint; prefix KV ~ N(0,1) written straig
 (inputs resident in HBM when the timed region starts; prefill is outside the metric, as in the
 reference: llama_glide.py:993-994).  tau is printed next to the rate because synthetic tau is not
 the published tau.  One JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, tau, config).  ``--full`` adds what the headline figure does not need: the event-bracketed rounds of the
+timed region and the roofline objects built from them, the vanilla-decode denominator and speed-up, the CPU baselines.
+``--dump-outputs DIR`` writes what the timed path handed back after its last step (token ids, speculation mask,
+counters; float64) as ``DIR/<name>.npy``: inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -324,6 +330,22 @@ def cpu_baseline_round(tree, layers_sample=4, prefix=4096, rounds=2):
                       f"of this random-weight model"}
 
 
+def dump_outputs(d, st, emitted_before_last):
+    """What a caller of the timed path receives (``tree_spec_generate`` / ``spec_generate`` return output_ids, count, num,
+    spec_mask), taken from the decode state after the last timed step, plus the tokens that step emitted.  Token ids are
+    exact in float64."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {
+        "output_ids": st.output_ids,
+        "spec_mask": st.spec_mask,
+        "last_step_tokens": st.output_ids[:, emitted_before_last:st.emitted],
+        "counters": torch.tensor([st.emitted, st.count, st.num]),          # emitted tokens, accepted draft tokens, rounds
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.detach().cpu().to(torch.float64).numpy())
+
+
 SAMPLE = 10      # every SAMPLE-th timed round is issued launch by launch with HIP events around the attention kernel (32 pairs)
 GSAMPLE = 20     # ... and every GSAMPLE-th also around the ~165 projection launches: an event record costs ~5 us of stream time
 
@@ -342,14 +364,21 @@ def main():
                     help="scale of the o_proj / down_proj weights of the random model (smaller = the draft agrees more often).  Default "
                          "0.02, and 0.01 for qwq-32b: a 64-layer residual stream drifts twice as far from the shared embedding, and "
                          "0.02 leaves tau = 1.3 there against ~3 for the 32/40-layer models (round 4: tau 3.0 at 0.01)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: event-bracketed rounds inside the timed region "
+                         "(roofline objects, per-rank kernel times), the vanilla-decode denominator and speed-up, the CPU baselines. "
+                         "The --no-* options below switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed (output_ids, spec_mask, the last step's "
+                         "tokens, counters) as DIR/<name>.npy in float64")
     ap.add_argument("--vanilla-steps", type=int, default=16)
     ap.add_argument("--cpu-sample-calls", type=int, default=64)     # bounded by time below: ~12 s of host time
-    ap.add_argument("--no-cpu-round", action="store_true", help="skip the full-round CPU baseline at configs[0] scale")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-vanilla", action="store_true", help="skip the vanilla-decode denominator (profiling runs)")
+    ap.add_argument("--no-cpu-round", action="store_true", help="--full: skip the full-round CPU baseline at configs[0] scale")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip both CPU baselines")
+    ap.add_argument("--no-vanilla", action="store_true", help="--full: skip the vanilla-decode denominator (profiling runs)")
     ap.add_argument("--no-graphs", action="store_true", help="issue every round launch by launch (no HIP-graph replay)")
     ap.add_argument("--no-kernel-timing", action="store_true",
-                    help="diagnostic: no event-bracketed rounds (no roofline objects): every round is a graph replay")
+                    help="--full, diagnostic: no event-bracketed rounds (no roofline objects): every round is a graph replay")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="diagnostic: gloo lets several ranks share ONE GPU (with --share-gpu) to exercise the N > 1 code path")
     ap.add_argument("--exchange", default="peer", choices=["peer", "collective"],
@@ -471,7 +500,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    timing = not args.no_kernel_timing        # every rank brackets the same rounds (round 4: the line carries per-rank figures)
+    # every rank brackets the same rounds (round 4: the line carries per-rank figures); a plain run replays every round
+    timing = args.full and not args.no_kernel_timing
     from longspec_amd import ops as _ops
 
     def fresh_state():
@@ -490,13 +520,16 @@ def main():
             for _ in range(args.warmup):
                 m.chain_round(cst)
             barrier()
-            tok0 = cst.emitted
+            tok0 = e_last = cst.emitted
             t0 = time.time()
             for _ in range(args.steps):
+                e_last = cst.emitted
                 m.chain_round(cst)
             barrier()
             elapsed = time.time() - t0
             tokens = cst.emitted - tok0
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, cst, e_last)
         out = {"metric": "accepted tokens/sec (chain speculative decode, gamma 4, temperature 0)", "value": round(tokens / elapsed, 3),
                "unit": "accepted tokens/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak" if weak else "strong",
@@ -557,11 +590,12 @@ def main():
             for _ in range(args.warmup):
                 m.tree_round(st)
             barrier()
-            tok0 = st.emitted
+            tok0 = e_last = st.emitted
             if pool is not None:
                 pool.on = gpool.on = True
             t0 = time.time()
             for i in range(args.steps):
+                e_last = st.emitted
                 if gpool is not None:                    # launches are bracketed on every 10th / 20th round only: two event
                     pool.on = (i % SAMPLE == 0)          # records around each of ~200 launches cost ~2 ms per round, and
                     if xpool is not None:
@@ -587,7 +621,7 @@ def main():
             if not agree:
                 detail = {"tokens_min_max": [int(lo[0]), int(chk[0])], "id_sum_min_max": [int(lo[1]), int(chk[1])]}
         return SimpleNamespace(elapsed=elapsed, tokens=tokens, st=st, graphs=graphs, pool=pool, gpool=gpool, xpool=xpool, agree=agree,
-                               detail=detail)
+                               detail=detail, e_last=e_last)
 
     res = measure()
     if world > 1 and shard.peer is not None:
@@ -609,6 +643,8 @@ def main():
     elapsed = float(t.item())
     tau = tokens / args.steps
     value = tokens / elapsed
+    if args.dump_outputs and rank == 0:                  # the round is replicated: rank 0's outputs are every rank's
+        dump_outputs(args.dump_outputs, st, res.e_last)
 
     out = {
         "metric": "accepted tokens/sec (tree speculative decode, temperature 0)", "value": round(value, 3),
@@ -718,7 +754,7 @@ def main():
         out["roofline_round"] = {"bound": "hbm", "achieved": round(r_ach, 2), "peak": 8000.0, "unit": "GB/s",
                                  "frac": round(r_ach / 8000.0, 4), "algorithmic_bytes_per_round": round(round_b),
                                  "of_which_weights": round(gemm_b), "of_which_kv": round(attn_b)}
-    if rank == 0 and world == 1 and not args.no_vanilla:
+    if args.full and rank == 0 and world == 1 and not args.no_vanilla:
         # ---- speed-up denominator: vanilla autoregressive decode on the same model and prefix ----------
         with torch.inference_mode():
             for layer in m.model.layers:

@@ -2,7 +2,7 @@
 # Writes gpurun_out/pmc_round_kernels.json: counters per launch + derived utilisations.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-ARGS="${BENCH_ARGS:---steps 4 --warmup 1 --no-vanilla --no-cpu-baseline --no-graphs}"
+ARGS="${BENCH_ARGS:---full --steps 4 --warmup 1 --no-vanilla --no-cpu-baseline --no-graphs}"
 i=0
 for grp in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_MFMA SQ_INSTS_VALU" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAVES"; do
