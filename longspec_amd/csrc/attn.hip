@@ -73,7 +73,7 @@ struct AttnK {
     int RB, KS, tile, bpw, nstages, nd, pp;
     // row blocks 0..rbA-1 have qtA tiles of 16 rows, the others qtB
     int rbA, qtA, qtB;
-    int pp_extra;       // ping-pong kernel: row tiles - 16 (the first pp_extra waves carry 3 tiles, the others 2)
+    int pp_extra;       // unused, always 0: removing it moves the fields below and re-allocates every kernel's SGPRs
     float scale;
     long q_sb, q_ss, q_sh;
     long kc_sb, kc_ss, kc_sh;
@@ -317,20 +317,12 @@ __device__ __forceinline__ void dma16(const void* src, char* lds_dst) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(base) : "memory", "m0");
 }
 
-// Cache policy of the streamed prefix K/V (every byte is used once per call by one workgroup): -DLS_KV_NT=1 requests it
-// non-temporally (MI355X_MICROARCH "nt-weights"; round 4 A/B on one box: verification call 0.4114 -> 0.4175 of the HBM roofline,
-// round 12.28 -> 12.15 ms); 0 = default policy.
-#ifndef LS_KV_NT
-#define LS_KV_NT 1
-#endif
-#if LS_KV_NT
-#define LS_KV_POLICY " nt"
-#else
-#define LS_KV_POLICY ""
-#endif
-// one K and one V piece (4 keys each) of the fast DMA path: wave-uniform 64-bit base, 32-bit per-lane offset
+// one K and one V piece (4 keys each) of the fast DMA path: wave-uniform 64-bit base, 32-bit per-lane offset.  Requested
+// non-temporally (`nt`): every byte of the streamed prefix K/V is used once per call by one workgroup (MI355X_MICROARCH
+// "nt-weights"; round 4 A/B on one box against the default policy: verification call 0.4114 -> 0.4175 of the HBM roofline,
+// round 12.28 -> 12.15 ms).
 __device__ __forceinline__ void dma16_s(const char* base_uniform, unsigned lane_off, unsigned lds_addr_uniform) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" LS_KV_POLICY
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt"
                  :
                  : "v"(lane_off), "s"(base_uniform), "s"(lds_addr_uniform)
                  : "memory", "m0");
@@ -846,38 +838,14 @@ __device__ __forceinline__ void partial_entry(const AttnK& p, char* smem) {
 // true row maxima, then the same loop with those.  K and V stream through separate rings of 32-key blocks
 // (global_load_lds from all 8 waves, one K and one V piece per wave and step): block b is issued LA steps
 // before its K is multiplied (step b-1) and its V slot is released two steps later.
-#ifndef LS_WS_HEADROOM
-#define LS_WS_HEADROOM 4
-#endif
-// Diagnostic builds only (tools/build_variant.py abl<N> -DLS_WS_ABLATE=<N>; results are WRONG by construction): parts of the
-// warp-specialised kernel's steady loop removed, to price them at the in-round clock (profiles/r5_attn_ceiling.md).
-//   1 no K/V DMA behind the first look-ahead blocks     2 no QK^T MFMAs     4 no P.V / row-sum MFMAs
-//   8 no soft-max VALU work (a constant P is stored)    16 no LDS fragment reads (K, V^T, P) in the loop
-#ifndef LS_WS_ABLATE
-#define LS_WS_ABLATE 0
-#endif
-#ifndef LS_PART_WT
-#define LS_PART_WT 1
-#endif
-// LS_WS_PF = 1 (round 5): the operand fragments of the NEXT step are requested from the LDS in FRONT of the step's barrier and
-// are NOT waited for there (lgkmcnt counts in order: the P stores in front of them are) -- the S wave's 8 K fragments of block
-// j+2, the O wave's 16 V^T fragment halves of block j -- so that their latency runs under the barrier and both waves have matrix
-// work the moment it releases them.  The in-round ablations (profiles/r5_ws_ablations_inround.log) price the exposed fragment
-// reads at 34 us of a 165 us call at 128k, as much as either half of the MFMAs.  Costs one block of DMA look-ahead: a block
-// must be complete one barrier earlier.  (Round 4's LS_WS_PIPE2 also moved the reads in front of the barrier, but waited for them
-// there and moved the DMA issue with them: slower.)
-#ifndef LS_WS_PF
-#define LS_WS_PF 0
-#endif
-constexpr int WS_HEADROOM = LS_WS_HEADROOM;     // octaves between the first-64-keys maximum and the fixed soft-max reference
+// (Round 5 requested the next step's fragments in front of the barrier: +4..7 % at 128k, +11 % at 16k -- an LDS DMA does not
+// issue past the wave's own outstanding LDS reads; profiles/r5_ws_pf.json.)
+constexpr int WS_HEADROOM = 4;                   // octaves between the first-64-keys maximum and the fixed soft-max reference
 constexpr int WS_QT = 5;                         // row tiles per pair
-constexpr int WS_PF = LS_WS_PF;                  // 1: fragments of the next step are fetched in front of the barrier (see LS_WS_PF)
-constexpr int WS_LA = 5 + WS_PF;                 // blocks of DMA look-ahead (80 KB of K+V in flight per CU)
-// Ring stages.  K: block b lives from step b-1-LA to step b-1;  V: ... to step b+1.  WS_PF reads a block's fragments one barrier
-// earlier, so both rings recycle a slot one step earlier and the SAME 14 slots carry one more block of look-ahead (the reads in
-// front of a barrier may still be in flight when the first DMA piece behind it is issued: that piece lands >= 1 us later).
-constexpr int WS_NK = WS_LA + 1 - WS_PF;
-constexpr int WS_NV = WS_LA + 3 - WS_PF;
+constexpr int WS_LA = 5;                         // blocks of DMA look-ahead (80 KB of K+V in flight per CU)
+// Ring stages.  K: block b lives from step b-1-LA to step b-1, LA + 1 slots;  V: ... to step b+1, LA + 3 slots.
+constexpr int WS_NK = 6;
+constexpr int WS_NV = 8;
 constexpr int WS_BLK_B = 32 * ROWB;              // 8 KB: 32 keys of K (or V)
 constexpr int WS_PBUF_B = 4 * WS_QT * 1024;      // one P buffer: 4 pairs x 5 row tiles x (64 lanes x 16 B)
 constexpr int WS_RING_B = (WS_NK + WS_NV) * WS_BLK_B;
@@ -896,30 +864,17 @@ __device__ __forceinline__ void qk_block_pf(f32x4 (&s)[2][QT], const typename E:
 #pragma unroll
     for (int k4 = 0; k4 < 4; ++k4)
 #pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-#if LS_WS_ABLATE & 16
-            kf[k4][kt] = qf[0][k4];
-#else
-            kf[k4][kt] = lds_read16<typename E::V8>(kb + ((k4 ^ kx) << 6) + kt * 16 * ROWB);
-#endif
-        }
+        for (int kt = 0; kt < 2; ++kt) kf[k4][kt] = lds_read16<typename E::V8>(kb + ((k4 ^ kx) << 6) + kt * 16 * ROWB);
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) s[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if LS_WS_ABLATE & 2
-#pragma unroll
-    for (int k4 = 0; k4 < 4; ++k4)
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) asm volatile("" ::"v"(kf[k4][kt]));       // (the fragment reads stay)
-#else
 #pragma unroll
     for (int k4 = 0; k4 < 4; ++k4)
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt) s[kt][qt] = E::mfma(kf[k4][kt], qf[qt][k4], s[kt][qt]);
-#endif
 }
 
 template <typename E, int QT, bool S_ROLE>           // QT row tiles per pair: 5 (17..20 tiles per row block), 3 (two row chunks of 12 tiles)
@@ -973,25 +928,10 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
     const int nblocks = max(0, min(b_begin + bps, nb_all) - b_begin);
     const int last_key = L - 1;
 
-    // one K piece and one V piece per wave: keys 4*wave .. 4*wave+3 of block b (LDS image swizzled on the source side)
-#ifdef LS_WS_PROF
-    // wall-clock profile of one S wave and one O wave (s_memrealtime: 100 MHz): per-phase sums over the steady steps,
-    // dumped into the (unused, prefix-only call) new_o region by workgroup (split 1, kv head 0) -- tools/ws_prof.py
-    unsigned long long prof[6] = {0, 0, 0, 0, 0, 0};
-    unsigned long long pt = 0;
-    unsigned long long marks[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // launch timeline of the wave (absolute 100 MHz ticks)
-#define WS_MARK(i) do { marks[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-    WS_MARK(0);                                                  // entry (after the address set-up above)
-#define WS_T0() do { pt = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define WS_TS(i) do { const unsigned long long n_ = __builtin_amdgcn_s_memrealtime(); prof[i] += n_ - pt; pt = n_; } while (0)
-#else
-#define WS_T0()
-#define WS_TS(i)
-#define WS_MARK(i)
-#endif
-    // one K piece and one V piece per wave and block.  Inside the cache (all but the split's last blocks) the source address is
-    // a wave-uniform base (SGPRs) plus ONE per-lane offset register per operand -- the source-side swizzle of a wave's piece
-    // does not depend on the block -- instead of 64-bit per-lane address arithmetic (measured: 106-136 ns of a 1.4 us step)
+    // one K piece and one V piece per wave and block: keys 4*wave .. 4*wave+3 of block b (LDS image swizzled on the source
+    // side).  Inside the cache (all but the split's last blocks) the source address is a wave-uniform base (SGPRs) plus ONE
+    // per-lane offset register per operand -- the source-side swizzle of a wave's piece does not depend on the block --
+    // instead of 64-bit per-lane address arithmetic (measured: 106-136 ns of a 1.4 us step)
     const int kq_ = lane >> 4, pos_ = lane & 15;
     const unsigned koff_ = (unsigned)(kq_ * kc_row) + ((pos_ ^ (((wave & 3) << 2) | kq_)) << 4);   // key & 15, key = 4*wave + kq_
     const unsigned voff_ = (unsigned)(kq_ * kc_row) + ((pos_ ^ ((((wave & 1) << 2) | kq_) << 1)) << 4);
@@ -1017,18 +957,16 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
         wait_vmcnt(need < nblocks ? 2 * younger : 0);
     };
     auto pass_head = [&]() {
-        const int n0 = min(nblocks, WS_NK);        // (WS_PF: block LA follows behind the look's barrier, `look_done`)
+        const int n0 = min(nblocks, WS_NK);
         for (int b = 0; b < n0; ++b) dma(b);
-        wait_block(1 + WS_PF, n0);                 // blocks 0 and 1 (reference look, first QK) [+ block 2: read in front of barrier 0]
+        wait_block(1, n0);                         // blocks 0 and 1 (reference look, first QK)
         __builtin_amdgcn_s_barrier();
     };
     auto step_head = [&](int j) {
-#if !(LS_WS_ABLATE & 1)
         if (j + 1 + WS_LA < nblocks) dma(j + 1 + WS_LA);                // its K slot died at step j-1, its V slot at step j-1
-#endif
     };
     auto step_tail = [&](int j) {
-        wait_block(j + 2 + WS_PF, min(nblocks, j + 2 + WS_LA));         // K(j+2) is multiplied at step j+1 (WS_PF: K(j+3) is read in front of barrier j+1)
+        wait_block(j + 2, min(nblocks, j + 2 + WS_LA));                 // K(j+2) is multiplied at step j+1
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // P writes / reads of this step are done
         __builtin_amdgcn_s_barrier();
     };
@@ -1084,7 +1022,6 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
             for (int qt = 0; qt < QT; ++qt)
                 if (mode != 2) mref[qt] = -INFINITY;
             pass_head();
-            WS_MARK(1);                            // blocks 0 and 1 have landed (Q loads issued before them)
             f32x4 s_cur[2][QT];
             if (mode == 0 && nblocks > 1) {        // block 1's share of the reference (block 0's follows)
                 qk_block<E, QT>(s_cur, qf, tb, k_addr(1));
@@ -1112,32 +1049,7 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
                 for (int qt = 0; qt < QT; ++qt)
                     if (row0 + qt * 16 + l15 >= p.M) mref[qt] = INFINITY;      // padding rows: p = 2^(0 - inf) = 0
             }
-            typename E::V8 kfr[4][2];              // WS_PF: the K fragments of the block whose scores the next step forms
-            auto load_kf = [&](unsigned kbase) {
-                int kx = tb.kx;
-                asm volatile("" : "+v"(kx));       // see qk_block
-                const unsigned kb = kbase + tb.kb;
-#pragma unroll
-                for (int k4 = 0; k4 < 4; ++k4)
-#pragma unroll
-                    for (int kt = 0; kt < 2; ++kt) kfr[k4][kt] = lds_read16<typename E::V8>(kb + ((k4 ^ kx) << 6) + kt * 16 * ROWB);
-            };
-            auto qk_from_kfr = [&](f32x4 (&sx)[2][QT]) {
-#pragma unroll
-                for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                    for (int qt = 0; qt < QT; ++qt) sx[kt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k4 = 0; k4 < 4; ++k4)
-#pragma unroll
-                    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-                        for (int kt = 0; kt < 2; ++kt) sx[kt][qt] = E::mfma(kfr[k4][kt], qf[qt][k4], sx[kt][qt]);
-            };
-            if (WS_PF && nblocks > 1) load_kf(k_addr(1));                     // (block 1 is complete since pass_head's barrier)
             __builtin_amdgcn_s_barrier();          // K(0) is consumed: step 0 may overwrite its slot
-            if (WS_PF && WS_LA < nblocks) dma(WS_LA);      // (the ring's last look-ahead block takes K(0)'s slot)
-            WS_MARK(2);                            // reference look done
             typedef __attribute__((address_space(3))) typename E::V8 lds_v8;
             // soft-max numerators of block j (reference mref, fixed) -> P(j) in LDS.  The row sums are NOT formed here: the
             // O wave gets them from the matrix pipe (a ninth V^T tile whose row 0 is all ones: l = sum of the fp16 P it
@@ -1148,17 +1060,11 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
                 for (int qt = 0; qt < QT; ++qt) {
                     const float mc = mref[qt] * c;
                     typename E::V8 pf;
-#if LS_WS_ABLATE & 8
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) pf[e] = E::from_f32(mc * 0.f + 0.001f * (float)(e + 1));
-                    asm volatile("" ::"v"(sc[0][qt]), "v"(sc[1][qt]));
-#else
 #pragma unroll
                     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
                             pf[kt * 4 + e] = E::from_f32(__builtin_amdgcn_exp2f(__builtin_fmaf(sc[kt][qt][e], c, -mc)));
-#endif
 #ifdef LS_MUTATE_SKIP_BLOCK
                     // MUTANT (tests/test_gpu_ops.py::test_mutant_is_caught, never the product build): one 32-key block of one
                     // split of one kv head contributes nothing
@@ -1176,12 +1082,7 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
                     if (j < nblocks) {
                         row_max(s_cur, mref);
                         if (j + 1 < nblocks) {
-                            if constexpr (WS_PF) {         // (the rings recycle K(j+1)'s slot at this step's head: fragments in registers)
-                                qk_from_kfr(s_cur);
-                                if (j + 2 < nblocks) load_kf(k_addr(j + 2));
-                            } else {
-                                qk_block_pf<E, QT>(s_cur, qf, tb, k_addr(j + 1));
-                            }
+                            qk_block_pf<E, QT>(s_cur, qf, tb, k_addr(j + 1));
                             mask_tail(s_cur, j + 1);
                         }
                     }
@@ -1191,46 +1092,24 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
                 // steady state: ONE basic block holds the QK^T MFMAs of block j+1 and the VALU work of block j, so that
                 // the scheduler can lay them out as asked below: an MFMA, then the VALU instructions its 16 cycles hide
                 auto step_ab = [&](int j, f32x4 (&s_in)[2][QT], f32x4 (&s_next)[2][QT], auto masked, auto fixed_wait) {
-                    WS_T0();
                     step_head(j);
-                    WS_TS(0);
-                    if constexpr (WS_PF) {
-                        // S^T of block j+1 from the fragments fetched in front of the last barrier, under the exponentials of block j
-                        qk_from_kfr(s_next);
-                        softmax_store(j, s_in);
+                    qk_block_pf<E, QT>(s_next, qf, tb, k_addr(j + 1));
+                    softmax_store(j, s_in);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);             // all 8 K-fragment LDS reads first,
+                    __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);            // VALU work while they are in flight
 #pragma unroll
-                        for (int i = 0; i < 8 * QT; ++i) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // 1 MFMA
-                            __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);     // 6 VALU
-                        }
-                        if constexpr (decltype(masked)::value) mask_tail(s_next, j + 1);
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (j + 2 < nblocks) load_kf(k_addr(j + 2));               // complete since barrier j-1; waited for by its first MFMA
-                    } else {
-                        qk_block_pf<E, QT>(s_next, qf, tb, k_addr(j + 1));
-                        softmax_store(j, s_in);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);         // all 8 K-fragment LDS reads first,
-                        __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);        // VALU work while they are in flight
-#pragma unroll
-                        for (int i = 0; i < 8 * QT; ++i) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // 1 MFMA
-                            __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);     // 6 VALU
-                        }
-                        if constexpr (decltype(masked)::value) mask_tail(s_next, j + 1);
+                    for (int i = 0; i < 8 * QT; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);         // 1 MFMA
+                        __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);         // 6 VALU
                     }
-                    WS_TS(1);
+                    if constexpr (decltype(masked)::value) mask_tail(s_next, j + 1);
                     // K(j+2) is multiplied at step j+1.  In the steady state exactly LA-1 younger blocks (2 pieces each) are in
                     // flight: one immediate wait instead of the compare / branch ladder of wait_block (measured: 155-170 ns of
                     // a 1.4 us step went into that ladder)
-                    if constexpr (decltype(fixed_wait)::value) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (WS_LA - 1 - WS_PF)) : "memory");
-                    else wait_block(j + 2 + WS_PF, min(nblocks, j + 2 + WS_LA));
-                    WS_TS(2);
-                    // the P stores are done (LDS operations of a wave complete in order: the 8 fragment reads behind them may still fly)
-                    if (WS_PF && j + 2 < nblocks) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-                    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    WS_TS(3);
+                    if constexpr (decltype(fixed_wait)::value) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (WS_LA - 1)) : "memory");
+                    else wait_block(j + 2, min(nblocks, j + 2 + WS_LA));
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // the P stores are done
                     __builtin_amdgcn_s_barrier();
-                    WS_TS(4);
                 };
                 // only the split's LAST block can cross the end of the cache: its masking (35 selects per lane when the
                 // compiler if-converts it into every iteration) is peeled off the loop
@@ -1269,7 +1148,6 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
             }
         };
         run_pass(0);
-        WS_MARK(3);                                        // step loop done
         if (tid == 0) *redo_flag = 0;
         __syncthreads();
         __syncthreads();                                   // (the O waves raise the flag in between)
@@ -1282,15 +1160,6 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
             run_pass(1);
             run_pass(2);
         }
-#ifdef LS_WS_PROF
-        WS_MARK(4);
-        if (!p.has_new && split == 1 && kvh == 0 && bi == 0 && wave == 0 && lane < 8)
-            reinterpret_cast<unsigned long long*>(p.new_o)[16 + lane] = marks[0] * (lane == 0) + marks[1] * (lane == 1) + marks[2] * (lane == 2) +
-                                                                        marks[3] * (lane == 3) + marks[4] * (lane == 4);
-        if (!p.has_new && split == 1 && kvh == 0 && bi == 0 && wave == 0 && lane < 6)
-            reinterpret_cast<unsigned long long*>(p.new_o)[lane] = prof[0] * (lane == 0) + prof[1] * (lane == 1) + prof[2] * (lane == 2) +
-                                                                   prof[3] * (lane == 3) + prof[4] * (lane == 4) + (unsigned long long)nblocks * (lane == 5);
-#endif
         float mcur[QT];                                    // the rows' reference after the corrections below (= mref without)
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) mcur[qt] = mref[qt];
@@ -1370,12 +1239,11 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
             }
             pass_head();
             __builtin_amdgcn_s_barrier();          // the S waves' look at blocks 0 and 1 is over
-            if (WS_PF && WS_LA < nblocks) dma(WS_LA);
             typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
             union VF {
                 struct { s16x4 a, b; } s;
                 typename E::V8 v;
-            } vf[8];                               // all 8 V^T fragments before the first MFMA (WS_PF: fetched in front of the last barrier)
+            } vf[8];                               // all 8 V^T fragments before the first MFMA
             auto load_vf = [&](int blk) {
                 int vx = tb.vx;
                 asm volatile("" : "+v"(vx));       // see qk_block
@@ -1383,45 +1251,25 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
 #pragma unroll
                 for (int dt = 0; dt < 8; ++dt) {
                     const unsigned va = vb + ((dt ^ vx) << 5);
-#if LS_WS_ABLATE & 16
-                    vf[dt].v = ones;
-                    asm volatile("" ::"v"(va));
-#else
                     vf[dt].s.a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)va);
                     vf[dt].s.b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(va + 16 * ROWB));
-#endif
                 }
             };
 #pragma unroll 1
             for (int j = 0; j <= nblocks; ++j) {
-                WS_T0();
                 step_head(j);
-                WS_TS(0);
                 if (mode != 1 && j >= 1) {
                     const int jj = j - 1;
                     typename E::V8 pf[QT];
 #pragma unroll
-                    for (int qt = 0; qt < QT; ++qt) {
-#if LS_WS_ABLATE & 16
-                        pf[qt] = ones;
-#else
-                        pf[qt] = lds_read16<typename E::V8>(p_base + (jj & 1) * WS_PBUF_B + qt * 1024);
-#endif
-                    }
-                    if constexpr (!WS_PF) load_vf(jj);
-#if LS_WS_ABLATE & 4
-#pragma unroll
-                    for (int dt = 0; dt < 8; ++dt) asm volatile("" ::"v"(vf[dt].v));
-#pragma unroll
-                    for (int qt = 0; qt < QT; ++qt) asm volatile("" ::"v"(pf[qt]));
-#else
+                    for (int qt = 0; qt < QT; ++qt) pf[qt] = lds_read16<typename E::V8>(p_base + (jj & 1) * WS_PBUF_B + qt * 1024);
+                    load_vf(jj);
 #pragma unroll
                     for (int dt = 0; dt < 8; ++dt)
 #pragma unroll
                         for (int qt = 0; qt < QT; ++qt) acc[dt][qt] = E::mfma(vf[dt].v, pf[qt], acc[dt][qt]);
 #pragma unroll
                     for (int qt = 0; qt < QT; ++qt) lacc[qt] = E::mfma(ones, pf[qt], lacc[qt]);
-#endif
                     if constexpr (SAT_FIX) {
                         // a saturated numerator adds >= 65504 to its row's sum: one comparison of the five rows' running total
                         // per step (7 vector instructions; any VALU work in this wave comes out of the SIMD the pair shares --
@@ -1438,26 +1286,14 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
                         sat_prev = tot;
                     }
                 }
-                if constexpr (WS_PF) {
-                    // V^T of block j, multiplied at step j+1 (the block is complete since barrier j-2): requested here, behind
-                    // this step's MFMAs, and not waited for in front of the barrier
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (mode != 1 && j < nblocks) load_vf(j);
-                }
-                WS_TS(1);
                 // steady state: exactly LA-1 younger blocks (2 pieces each) are in flight behind K(j+2) -- see the S role
-                if (j + 2 + WS_LA <= nblocks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (WS_LA - 1 - WS_PF)) : "memory");
-                else wait_block(j + 2 + WS_PF, min(nblocks, j + 2 + WS_LA));
-                WS_TS(2);
-                // (WS_PF: the P fragments of this step were consumed by its MFMAs; only the fragment reads above are outstanding)
-                if constexpr (!WS_PF) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                WS_TS(3);
+                if (j + 2 + WS_LA <= nblocks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (WS_LA - 1)) : "memory");
+                else wait_block(j + 2, min(nblocks, j + 2 + WS_LA));
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
-                WS_TS(4);
             }
         };
         run_pass(0);
-        WS_MARK(3);
         __syncthreads();
         {   // an fp16 P that overflowed (or an inf - inf behind it) leaves a non-finite row sum: redo with the true row maxima
             bool bad = false;
@@ -1471,11 +1307,6 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
             run_pass(1);
             run_pass(2);
         }
-#ifdef LS_WS_PROF
-        if (!p.has_new && split == 1 && kvh == 0 && bi == 0 && wave == 4 && lane < 6)
-            reinterpret_cast<unsigned long long*>(p.new_o)[8 + lane] = prof[0] * (lane == 0) + prof[1] * (lane == 1) + prof[2] * (lane == 2) +
-                                                                       prof[3] * (lane == 3) + prof[4] * (lane == 4) + (unsigned long long)nblocks * (lane == 5);
-#endif
         if constexpr (SAT_FIX) {
             const int nwords = min(WS_SAT_WORDS, (nblocks + 31) >> 5);
             for (int w = 0; w < nwords; ++w) {
@@ -1521,12 +1352,9 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
             }
         }
         __syncthreads();                           // the pair's m*scale is in LDS
-        WS_MARK(5);                                // ready to write the partial
-#if LS_PART_WT
         // this (split, batch element)'s slab of the partials as a buffer resource: [sq][H][D] fp32, < 4 GB by construction
         const __amdgpu_buffer_rsrc_t part_rs = __builtin_amdgcn_make_buffer_rsrc(
             p.parts_o + ((long)split * p.b + bi) * p.sq * p.H * D, 0, p.sq * p.H * D * 4, 0x00020000);
-#endif
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             const float lt = __shfl(lacc[qt][0], l15);       // (lanes g4 == 0 hold it)
@@ -1537,34 +1365,21 @@ __device__ __forceinline__ void prefix_path_ws(const AttnK& p, char* smem, int s
                 if (g4 == 0)
                     p.parts_lse[(((long)split * p.b + bi) * p.H + head) * p.sq + rrow[qt]] =
                         lt > 0.f ? s_inv[pair * 80 + qt * 16 + l15] + __logf(lt) : -INFINITY;
-                float* op = p.parts_o + ((((long)split * p.b + bi) * p.sq + rrow[qt]) * p.H + head) * D + g4 * 4;
 #pragma unroll
                 for (int dt = 0; dt < 8; ++dt) {
-#if LS_PART_WT
                     // the partials leave the L2 as they are written (agent-scope write-through, `sc1` = aux 16) instead of in one
                     // write-back burst at the end of the kernel: 37.6 MB of dirty lines cost the launch ~2 us at its end
-                    // (round 5 A/B inside the round, profiles/r5_part_wt.json; -DLS_PART_WT=0 rebuilds the plain-store variant;
-                    // `nt` stores were slower, round 4).  Through the compiler's buffer-store builtin, NOT inline asm: a VALU
-                    // write of a > 64-bit store's data registers needs two wait states behind the store, which the compiler only
-                    // inserts for stores it knows -- the asm form of this line gave wrong partials in one build and right ones
-                    // in another.
+                    // (round 5 A/B inside the round against plain stores, profiles/r5_part_wt.json; `nt` stores were slower,
+                    // round 4).  Through the compiler's buffer-store builtin, NOT inline asm: a VALU write of a > 64-bit store's
+                    // data registers needs two wait states behind the store, which the compiler only inserts for stores it
+                    // knows -- the asm form of this line gave wrong partials in one build and right ones in another.
                     typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
                     const f32x4 v_ = acc[dt][qt] * inv;
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v_), part_rs,
                                                            (unsigned)((((long)rrow[qt] * p.H + head) * D + g4 * 4 + dt * 16) * 4), 0, 16);
-#else
-                    *reinterpret_cast<f32x4*>(op + dt * 16) = acc[dt][qt] * inv;
-#endif
                 }
             }
         }
-#ifdef LS_WS_PROF
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        WS_MARK(6);                                // partial stores acknowledged
-        if (!p.has_new && split == 1 && kvh == 0 && bi == 0 && wave == 4 && lane < 8)
-            reinterpret_cast<unsigned long long*>(p.new_o)[24 + lane] = marks[0] * (lane == 0) + marks[3] * (lane == 3) +
-                                                                        marks[5] * (lane == 5) + marks[6] * (lane == 6);
-#endif
     }
 }
 
@@ -1594,15 +1409,6 @@ __global__ __launch_bounds__(MAX_THREADS) void attn_partial_ws_kernel(const Attn
     }
     drain_lds_dma();
 }
-
-// The two measured negatives of round 3 (four-wave and ping-pong kernels) live in tools/mb/ and are only compiled into
-// diagnostic variants (tools/build_variant.py w4 -DLS_WITH_W4 / pp -DLS_WITH_PP); the product never dispatches them.
-#ifdef LS_WITH_W4
-#include "../../tools/mb/attn_w4_kernel.inc"
-#endif
-#ifdef LS_WITH_PP
-#include "../../tools/mb/attn_pp_kernel.inc"
-#endif
 
 // Row blocks 0..rbA-1 carry QTA tiles, the rest QTB: both instantiations execute the same barrier
 // sequence (identical tile loop), so a workgroup may mix them wave by wave.
@@ -1864,8 +1670,7 @@ __global__ void pack_mask_kernel(const int64_t* mask, int M, int N, uint32_t* bi
 // ---- host side ---------------------------------------------------------------------------
 struct Cfg {
     int qtA, qtB, rbA, RB, KS, tile, bpw, nstages, nd, pp, row_chunks, rows_per_chunk, threads, lds;
-    int ws;        // 1: warp-specialised prefix path (attn_partial_ws_kernel), 2: ping-pong (attn_partial_pp_kernel)
-    int pp_extra;
+    bool ws;       // warp-specialised prefix path (attn_partial_ws_kernel)
     int ws_qt;     // row tiles per S/O pair of the warp-specialised kernel
 };
 
@@ -1873,42 +1678,28 @@ struct Cfg {
 // The warp-specialised kernel takes the verification-sized row blocks (17..20 tiles) of calls whose prefix has
 // no causal / window edge (every row sees keys [0, L)) and whose new block fits its smaller ring.
 // Which streaming kernel serves verification-sized row blocks: LS_ATTN_KERNEL = ws (default) | general, read ONCE per
-// process (A/B switch of the benchmarks).
-int kernel_choice() {       // 0 general, 1 warp-specialised (round 2), 2 ping-pong (round 3)
-    static const int choice = [] {
+// process (A/B switch of the benchmarks).  True: the warp-specialised kernel is enabled.
+bool ws_kernel_enabled() {
+    static const bool enabled = [] {
         const char* e = getenv("LS_ATTN_KERNEL");
-        if (e && e[0] == 'g') return 0;
-#ifdef LS_WITH_W4
-        if (e && e[0] == 'f') return 3;          // four-wave kernel (round 3, measured negative)
-#endif
-#ifdef LS_WITH_PP
-        if (e && e[0] == 'p') return 2;
-#endif
-        return 1;
+        return !(e && e[0] == 'g');
     }();
-    return choice;
+    return enabled;
 }
 
 bool ws_eligible(const ls_attn_desc* d) {
-    if (kernel_choice() < 1) return false;
+    if (!ws_kernel_enabled()) return false;
     // causal with ALL query rows appended (the chunks of a long prompt, ops._prefill_attention_batched): the diagonal lives
     // in the new-key block and every row sees the whole prefix -- hi(r) = min(L, r + sk - sq + 1) = L when sk = L + sq.
     // Only for long prompts: short ones keep the kernel (and the rounding) the goldens were generated against.
     const bool append_chunk = d->causal != 0 && d->new_mode == LS_NEW_FLASH && d->n_app == d->sq && d->kv_len_hint >= 4096;
-    int cap = WS_NEW_CAP;
-#ifdef LS_WITH_PP
-    if (kernel_choice() == 2) cap = PP_NEW_CAP;
-#endif
-#ifdef LS_WITH_W4
-    if (kernel_choice() == 3) cap = W4_NEW_CAP;
-#endif
-    return (d->causal == 0 || append_chunk) && d->window_left < 0 && (d->new_mode == LS_NEW_NONE || d->n_new <= cap / 64 * 64);
+    return (d->causal == 0 || append_chunk) && d->window_left < 0 &&
+           (d->new_mode == LS_NEW_NONE || d->n_new <= WS_NEW_CAP / 64 * 64);
 }
 
 Cfg pick_cfg(int M, bool ws_ok, bool long_prefix) {
     Cfg c;
-    c.ws = 0;
-    c.pp_extra = 0;
+    c.ws = false;
     c.ws_qt = WS_QT;
     int tiles = (M + 15) / 16;
     c.row_chunks = 1;
@@ -1916,7 +1707,7 @@ Cfg pick_cfg(int M, bool ws_ok, bool long_prefix) {
         c.row_chunks = (M + 319) / 320;
         tiles = 20;
     }
-    const bool ws2 = ws_ok && long_prefix && kernel_choice() == 1 && tiles > 20 && tiles <= 24;
+    const bool ws2 = ws_ok && long_prefix && tiles > 20 && tiles <= 24;
     // 21..24 row tiles (GQA-5 x 74 verification rows = 370: QwQ) run as TWO row chunks of 12 tiles on the warp-specialised
     // kernel with 3 tiles per S/O pair: six tiles per pair do not fit the S wave's registers (96 for Q^T alone), and the general
     // kernel that served this shape until round 3 ran it at 0.23 of the HBM roofline.  The chunks re-read the K/V stream (from
@@ -1939,32 +1730,13 @@ Cfg pick_cfg(int M, bool ws_ok, bool long_prefix) {
     c.rows_per_chunk = (c.rbA * c.qtA + (c.RB - c.rbA) * c.qtB) * 16;
     c.threads = nw * 64;
     c.lds = c.nstages * 2 * c.tile * ROWB + 16;
-#ifdef LS_WITH_PP
-    if (ws_ok && kernel_choice() == 2 && tiles > 16 && tiles <= 24 && c.row_chunks == 1) {
-        c.ws = 2;                                   // ping-pong kernel: 8 waves, 3 or 2 row tiles each
-        c.nstages = PP_NEW_CAP / c.tile;            // the new-block workgroup's capacity in this ring
-        c.lds = PP_LDS;
-        c.pp_extra = tiles - 16;
-    } else
-#endif
-#ifdef LS_WITH_W4
-    if (ws_ok && kernel_choice() == 3 && tiles > 16 && tiles <= 20 && c.row_chunks == 1) {
-        c.ws = 3;                                   // four-wave kernel: 4 waves x 5 row tiles
-        c.qtA = c.qtB = 5; c.RB = 4; c.rbA = 4; c.KS = 1;
-        c.rows_per_chunk = 320;
-        c.threads = 256;
-        c.nd = 4;
-        c.nstages = W4_NEW_CAP / c.tile;
-        c.lds = W4_LDS;
-    } else
-#endif
     if (ws2) {
-        c.ws = 1;
+        c.ws = true;
         c.ws_qt = 3;
         c.nstages = WS_NEW_CAP / c.tile;
         c.lds = WS_LDS;
     } else if (ws_ok && tiles > 16 && tiles <= 20) {       // row split of the new-key block stays 3,3,3,3,2,2,2,2
-        c.ws = 1;
+        c.ws = true;
         c.nstages = WS_NEW_CAP / c.tile;            // the new-block workgroup's capacity in the smaller ring
         c.lds = WS_LDS;
     }
@@ -2079,40 +1851,8 @@ int launch_partial_ws(const Cfg& c, const AttnK& k, dim3 grid, hipStream_t s) {
     return LS_OK;
 }
 
-#ifdef LS_WITH_PP
-template <typename E>
-int launch_partial_pp(const Cfg& c, const AttnK& k, dim3 grid, hipStream_t s) {
-    auto fn = attn_partial_pp_kernel<E>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)attr;
-    hipLaunchKernelGGL(fn, grid, dim3(c.threads), c.lds, s, k);
-    LS_CHECK_LAUNCH("attn_partial_pp_kernel");
-    return LS_OK;
-}
-#endif
-
-#ifdef LS_WITH_W4
-template <typename E>
-int launch_partial_w4(const Cfg& c, const AttnK& k, dim3 grid, hipStream_t s) {
-    auto fn = attn_partial_w4_kernel<E>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)attr;
-    hipLaunchKernelGGL(fn, grid, dim3(c.threads), c.lds, s, k);
-    LS_CHECK_LAUNCH("attn_partial_w4_kernel");
-    return LS_OK;
-}
-#endif
-
 template <typename E>
 int dispatch_partial(const Cfg& c, const AttnK& k, dim3 grid, hipStream_t s) {
-#ifdef LS_WITH_W4
-    if (c.ws == 3) return launch_partial_w4<E>(c, k, grid, s);
-#endif
-#ifdef LS_WITH_PP
-    if (c.ws == 2) return launch_partial_pp<E>(c, k, grid, s);
-#endif
     if (c.ws) return c.ws_qt == 3 ? launch_partial_ws<E, 3>(c, k, grid, s) : launch_partial_ws<E, WS_QT>(c, k, grid, s);
     if (c.qtA == 1) return launch_partial<E, 1, 1>(c, k, grid, s);
     if (c.qtA == 2) return launch_partial<E, 2, 2>(c, k, grid, s);
@@ -2159,7 +1899,7 @@ int run_partial(const ls_attn_desc* d, void* ws, size_t ws_bytes, hipStream_t s,
     k.rows_per_chunk = c.rows_per_chunk;
     k.RB = c.RB; k.KS = c.KS; k.tile = c.tile; k.bpw = c.bpw; k.nstages = c.nstages; k.nd = c.nd; k.pp = c.pp;
     k.rbA = c.rbA; k.qtA = c.qtA; k.qtB = c.qtB;
-    k.pp_extra = c.pp_extra;
+    k.pp_extra = 0;
     k.scale = d->softmax_scale;
     k.q_sb = d->q_stride_b; k.q_ss = d->q_stride_s; k.q_sh = d->q_stride_h;
     k.kc_sb = d->kc_stride_b; k.kc_ss = d->kc_stride_s; k.kc_sh = d->kc_stride_h;
@@ -2231,7 +1971,7 @@ int ls_attn_num_parts(const ls_attn_desc* d) {
 const char* ls_attn_kernel_name(const ls_attn_desc* d) {
     if (validate(d)) return "invalid";
     const Cfg c = pick_cfg(d->H / d->Hkv * d->sq, ws_eligible(d), d->kv_len_hint >= 4096);
-    return c.ws == 3 ? "attn_partial_w4_kernel" : c.ws == 2 ? "attn_partial_pp_kernel" : c.ws ? "attn_partial_ws_kernel" : "attn_partial_kernel";
+    return c.ws ? "attn_partial_ws_kernel" : "attn_partial_kernel";
 }
 
 long ls_attn_redo_count(int reset) {

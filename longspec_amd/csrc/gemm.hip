@@ -38,23 +38,14 @@
 #include <stdlib.h>
 
 #include "ls_common.h"
-#ifdef LS_WITH_TAIL
-#define LS_TAIL_PART 0
-#include "../../tools/mb/layer_tail_kernel.inc"
-#undef LS_TAIL_PART
-#endif
 
 namespace {
 
 constexpr int GEMM_THREADS = 256;
-// Bytes of padding between the 64-row groups of a packed weight (experiment hook, 0 in the product).  The groups lie
-// nks * 4 KB apart -- 512 KB for K = 4096 -- and the workgroups of a launch walk them at the same pace; an 8 MB stride
-// between the splits costs the attention 9 % (tools/sweep_cross_attn_128k.py).  Here it does not: 256 B, 4 KB and 36 KB of
-// padding all measured within +-2 us of the unpadded layout on every projection (profiles/r3_gemm_group_pad.txt).
-#ifndef LS_GEMM_GROUP_PAD
-#define LS_GEMM_GROUP_PAD 0
-#endif
-constexpr long GROUP_PAD = LS_GEMM_GROUP_PAD;
+// (The 64-row groups of a packed weight lie nks * 4 KB apart -- 512 KB for K = 4096 -- and the workgroups of a launch walk
+// them at the same pace.  An 8 MB stride between the splits costs the attention 9 % (tools/sweep_cross_attn_128k.py); here
+// 256 B, 4 KB and 36 KB of padding between the groups all measured within +-2 us of the unpadded layout on every projection,
+// round 3, profiles/r3_gemm_group_pad.txt.)
 constexpr int COUNTER_BYTES = 64 * 1024;   // fixed counter region at the head of the workspace (16384 slabs)
 
 struct GemmK {
@@ -106,24 +97,11 @@ __device__ __forceinline__ f32x4 ld_coherent4(__amdgpu_buffer_rsrc_t r, unsigned
 
 // The weight stream: every byte is read ONCE per launch by ONE workgroup, so it is requested non-temporally
 // (`global_load_dwordx4 ... nt`: no allocation priority in L2 / MALL -- the x rows, the partials and the next kernel's
-// operands keep the cache).  MI355X_MICROARCH "nt-weights": issue -> landed -18 %, 5-10 % per decode layer.
-// -DLS_GEMM_NT=0 builds the default-policy variant for A/B runs (tools/build_variant.py).
-#ifndef LS_GEMM_NT
-#define LS_GEMM_NT 1
-#endif
-// -DLS_GEMM_KSTEP8=1: k-step-granular sets for the 128-row variant (24 KB per wave in flight instead of one 16 KB chunk of
-// look-ahead).  Round-4 A/B on one box: lm_head 202 vs 207 us, gate|up+SiLU 47.0 vs 45.4 us, GEMM per round 5.57-5.72 vs
-// 5.60-5.65 ms -- no gain: the 128-row launches are not limited by their look-ahead.  Default: the round-3 pipeline.
-#ifndef LS_GEMM_KSTEP8
-#define LS_GEMM_KSTEP8 0
-#endif
+// operands keep the cache).  MI355X_MICROARCH "nt-weights": issue -> landed -18 %, 5-10 % per decode layer against the
+// default policy.
 template <typename V>
 __device__ __forceinline__ V load_w(const char* p) {
-#if LS_GEMM_NT
     return __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
-#else
-    return *reinterpret_cast<const V*>(p);
-#endif
 }
 
 // MT = 16-row tiles of x (M <= 16*MT); NT = 16-row weight tiles per workgroup (4: one packed slab, 8: two)
@@ -135,13 +113,13 @@ __global__ __launch_bounds__(GEMM_THREADS, MT >= 5 ? 1 : 2) void skinny_gemm_ker
     using V4 = typename E::V4;
     // chunks (2 k-steps = 64 k; NT x 2 KB of W) of look-ahead per wave.  M <= 32: 2 waves per SIMD (256
     // registers each); above: 1 wave per SIMD with the full 512.
-    // A W register set ("unit") holds KPS k-steps of the workgroup's NT tiles: a whole 64-k chunk (2 k-steps x 4 tiles) for
-    // the 64-row variants, ONE k-step x 8 tiles for the 128-row variant -- 32 registers either way, so that the 128-row
-    // launches (gate|up, lm_head) keep three sets = 24 KB per wave in flight like the others instead of one 16 KB chunk
-    // (round 4: they streamed at 5.2 TB/s against 5.9 for the 64-row launches of the same pass).
-    constexpr int KPS = (NT == 8 && LS_GEMM_KSTEP8) ? 1 : 2;
+    // A W register set ("unit") holds KPS = 2 k-steps, a whole 64-k chunk, of the workgroup's NT tiles.  (Round 4 gave the
+    // 128-row variant k-step-granular sets instead, 24 KB per wave in flight instead of one 16 KB chunk of look-ahead: lm_head
+    // 202 vs 207 us, gate|up+SiLU 47.0 vs 45.4 us, GEMM per round 5.57-5.72 vs 5.60-5.65 ms -- no gain, the 128-row launches
+    // are not limited by their look-ahead; profiles/r4_ab_kstep8_*.json.)
+    constexpr int KPS = 2;
     constexpr int UPC = 2 / KPS;             // units per 64-k chunk of x
-    constexpr int LAC = NT == 8 ? (KPS == 1 ? 3 : 1) : MT == 1 ? 4 : 3;      // units of look-ahead
+    constexpr int LAC = NT == 8 ? 1 : MT == 1 ? 4 : 3;      // units of look-ahead
     constexpr int NCS = LAC + 1;             // W register sets, one per unit in flight
     static_assert(NCS % UPC == 0, "the x-chunk phase of a unit must be static inside the unrolled loop");
     constexpr int XL = 2 * MT;               // 1 KB pieces (8 rows x 128 B) of one x chunk
@@ -168,7 +146,7 @@ __global__ __launch_bounds__(GEMM_THREADS, MT >= 5 ? 1 : 2) void skinny_gemm_ker
     int n_lim;                   // end of the valid output columns of this slab's segment (global column)
     int n_tile0;                 // global output column of tile 0
     int seg_base = 0, seg = 0;
-    const long group_b = (long)p.nks * 4096 + GROUP_PAD;
+    const long group_b = (long)p.nks * 4096;
     {
         const int row0 = slab * NT * 16;                 // first packed row of the workgroup (global over segments)
         if (EPI != EPI_SILU_MUL) {
@@ -515,12 +493,7 @@ __global__ __launch_bounds__(GEMM_THREADS, MT >= 5 ? 1 : 2) void skinny_gemm_ker
     }
 }
 
-// (round 4's persistent layer-tail launch lives in tools/mb/layer_tail_kernel.inc: measured not faster, diagnostic variants only)
-#ifdef LS_WITH_TAIL
-#define LS_TAIL_PART 1
-#include "../../tools/mb/layer_tail_kernel.inc"
-#undef LS_TAIL_PART
-#endif
+// (Round 4's persistent layer-tail launch measured not faster: profiles/r4_tail_*.json.)
 
 // ---- weight packing ---------------------------------------------------------------------
 // The 64 rows of slab g at k-step s form one contiguous 4 KB block of 4 tiles:
@@ -549,7 +522,7 @@ __global__ __launch_bounds__(256) void pack_weight_kernel(const uint16_t* __rest
         }
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
         if (row < N) v = *reinterpret_cast<const uint4*>(src + (long)row * K + ks * 32 + (l >> 4) * 8);
-        *reinterpret_cast<uint4*>(out + blk * 512 + (long)g * (GROUP_PAD / 2) + l * 8) = v;
+        *reinterpret_cast<uint4*>(out + blk * 512 + l * 8) = v;
     }
 }
 
@@ -690,19 +663,13 @@ int launch_mt4(const GemmK& k, const Plan& pl, hipStream_t s) {      // epilogue
     }
 }
 
-#ifdef LS_WITH_TAIL
-#define LS_TAIL_PART 2
-#include "../../tools/mb/layer_tail_kernel.inc"
-#undef LS_TAIL_PART
-#endif
-
 }  // namespace
 
 extern "C" {
 
 size_t ls_linear_packed_bytes(int N, int K) {
     if (N < 1 || K < 32 || K % 32 != 0) return 0;
-    return (size_t)((N + 63) / 64) * (64 * (size_t)K * 2 + (size_t)GROUP_PAD);
+    return (size_t)((N + 63) / 64) * (64 * (size_t)K * 2);
 }
 
 static int pack_impl(const void* w, const void* w_up, void* packed, int N, int K, int dtype, void* stream, const char* what,
@@ -800,11 +767,5 @@ int ls_linear_prefetch(const ls_linear_desc* d, int units, void* workspace, size
     if (units < 1) LS_FAIL(LS_ERR_INVALID_ARG, "ls_linear_prefetch: units");
     return linear_launch(d, workspace, workspace_bytes, stream, units);
 }
-
-#ifdef LS_WITH_TAIL
-#define LS_TAIL_PART 3
-#include "../../tools/mb/layer_tail_kernel.inc"
-#undef LS_TAIL_PART
-#endif
 
 }  // extern "C"
