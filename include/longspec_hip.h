@@ -209,6 +209,44 @@ int ls_linear_fwd(const ls_linear_desc* d, void* workspace, size_t workspace_byt
  * attention finish) occupies the stream, it takes the HBM ramp off the projection that follows. */
 int ls_linear_prefetch(const ls_linear_desc* d, int units, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the same linear layers with 8-bit (OCP e4m3fn) weights -------------------------------------
+ *
+ * W[n, k] = q[n, k] * scale[n]: one e4m3fn byte per element (gfx950's FP8, not MI300's fnuz) and one fp32 scale per
+ * output row.  Activations, bias, accumulation (fp32, MFMA f16/bf16) and every rounding point are those of
+ * ls_linear_fwd; only the weight stream is half as long.  No counterpart in the reference (longspec/test keeps 16-bit
+ * weights); the seams served are ls_linear_fwd's: llama.py:361-363,390, LlamaMLP.forward (vendored qwen2.py:218-230),
+ * llama_glide.py:248-250,268,285-287,305, lm_head at llama_glide.py:960,1019,1046,1091.
+ *
+ * With power-of-two scales, q * scale is exactly representable in fp16 / bf16 and ls_linear_w8_fwd is BIT-IDENTICAL to
+ * ls_linear_fwd on the de-quantised 16-bit weight for the same descriptor (same n_splits): the launch plan and the k order
+ * of every row are shared.
+ *
+ * Packed layout: ceil(N/64)*64 * K bytes; the 1 KB block of (64-row group g, 64-wide k chunk c, 16-row tile t) sits at
+ * byte offset ((g*(K/64) + c)*4 + t)*1024 and holds, for lane l, the 8 bytes q[64g + 16t + l%16][64c + 8(l/16) .. +8]
+ * at offset 16*l and the 8 bytes q[same row][64c + 32 + 8(l/16) .. +8] at offset 16*l + 8 (rows >= N are zero). */
+size_t ls_linear_w8_packed_bytes(int N, int K);
+
+/* Row-wise quantiser: weight [N, K] dtype (row-major, contiguous, K % 8 == 0) -> q [N, K] e4m3fn bytes, scale [N] fp32.
+ *   amax = max_k |w[n,k]|;  scale[n] = 2^ceil(log2(amax / 448))  (pow2_scale != 0; exponent arithmetic, exponent >= -120)
+ *                           scale[n] = amax / 448                 (pow2_scale == 0);   amax == 0 -> scale = 1
+ *   q[n,k] = e4m3fn(w[n,k] / scale[n]), round to nearest even, saturating at +-448 (never the NaN encoding).
+ * Bit for bit what longspec_amd/quant.py::quantize_rows_e4m3 computes on the host. */
+int ls_linear_w8_quantize(const void* weight, int N, int K, int dtype, int pow2_scale, uint8_t* q, float* scale,
+                          void* stream);
+
+/* q [N, K] bytes -> the streamed layout (K % 64 == 0).  q_up != NULL: a gate/up pair of an MLP with alternating 16-row
+ * tiles (2N rows, N % 16 == 0: the operand of LS_EPI_SILU_MUL, as ls_linear_pack_gate_up).  rope != 0: the q/k layout
+ * of LS_EPI_QKV_ROPE (N = heads x 128, as ls_linear_pack_rope). */
+int ls_linear_w8_pack(const uint8_t* q, const uint8_t* q_up, void* packed, int N, int K, int rope, void* stream);
+
+/* As ls_linear_workspace_bytes / ls_linear_fwd with d->w[i] pointing at 8-bit packed segments (d->dtype is the
+ * activation / output dtype) and scale[i] the fp32 [n[i]] row scales of segment i, 16-byte aligned (LS_EPI_SILU_MUL:
+ * scale[0] = the gate rows', scale[1] = the up rows').  y = round(acc * scale[n] (+ bias[n])), then the epilogue.  The
+ * folded RMSNorm fields (norm_weight, ssq_in, ssq_out) are LS_ERR_UNSUPPORTED here, and there is no prefetch call. */
+size_t ls_linear_w8_workspace_bytes(const ls_linear_desc* d);
+int ls_linear_w8_fwd(const ls_linear_desc* d, const float* const scale[3], void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* ---- RMSNorm / RoPE (K8, K9) ------------------------------------------------ */
 
 /* LlamaRMSNorm.forward (transformers; imported at longspec/test/llama.py:36; vendored

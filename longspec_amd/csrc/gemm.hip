@@ -538,10 +538,7 @@ int num_cus_gemm() {
     return n;
 }
 
-struct Plan {
-    int MT, NT, nslabs, S, nks, N, flag_off;
-    size_t lds, counter_bytes, part_bytes;
-};
+using Plan = GemmPlan;       // ls_common.h: gemm_w8.hip launches the same plan
 
 int pick_mt(int M) { return M <= 16 ? 1 : M <= 32 ? 2 : M <= 80 ? 5 : 0; }
 
@@ -664,6 +661,8 @@ int launch_mt4(const GemmK& k, const Plan& pl, hipStream_t s) {      // epilogue
 }
 
 }  // namespace
+
+int gemm_make_plan(const ls_linear_desc* d, GemmPlan& pl) { return make_plan(d, pl); }
 
 extern "C" {
 

@@ -143,6 +143,15 @@ __device__ __forceinline__ float round_to(float x) {
     return E::to_f32(E::from_f32(x));
 }
 
+// ---- launch plan of the skinny GEMM (gemm.hip::make_plan), shared with the 8-bit-weight kernel (gemm_w8.hip): slab height,
+// split-K factor and LDS layout are functions of (M, N, K, epilogue, n_splits) ONLY, never of the weight format, so a row's k
+// order -- and with it every bit of the result -- is the same in both kernels.
+struct GemmPlan {
+    int MT, NT, nslabs, S, nks, N, flag_off;
+    size_t lds, counter_bytes, part_bytes;
+};
+int gemm_make_plan(const ls_linear_desc* d, GemmPlan& pl);      // validates `d` (LS_ERR_* + message) and fills `pl`
+
 __device__ __forceinline__ float wave_xor_max_16_32(float v) {
     v = fmaxf(v, __shfl_xor(v, 16));
     v = fmaxf(v, __shfl_xor(v, 32));

@@ -15,6 +15,7 @@ operators; the product default is the HIP operator layer, which raises on CPU te
 """
 from __future__ import annotations
 
+import os
 from types import SimpleNamespace
 from typing import Optional
 
@@ -81,26 +82,77 @@ class LlamaRMSNorm(nn.Module):
         return self.ops.rmsnorm(hidden_states, self.weight, self.variance_epsilon)
 
 
+WEIGHT_QUANT_ENV = "LONGSPEC_WEIGHT_QUANT"     # "fp8": every projection, "fp8-draft": the draft layer only; unset: 16-bit
+_ENV_SCOPES = {"fp8": ("draft", "target"), "fp8-draft": ("draft",)}
+
+
+def _env_quant_scopes():
+    mode = os.environ.get(WEIGHT_QUANT_ENV, "")
+    if mode and mode not in _ENV_SCOPES:
+        raise ValueError(f"{WEIGHT_QUANT_ENV}={mode!r}: expected one of {sorted(_ENV_SCOPES)}")
+    return _ENV_SCOPES.get(mode, ())
+
+
 class DecodeLinear(nn.Linear):
     """``nn.Linear`` (same parameters, same state_dict keys).  A call with <= 80 token rows on the GPU
     streams a packed copy of the weight (MFMA operand order, built once per weight version) through
-    ``ops.linear``; anything else is ``F.linear``."""
+    ``ops.linear``; anything else is ``F.linear``.
+
+    Weight mode ``weight_quant``: ``None`` (16-bit) or ``"fp8"`` (``quantize_weight_``): ``.weight`` then holds the
+    e4m3-rounded values ``q * 2^e`` -- exact in fp16 / bf16 -- and the decode-shaped path streams the 8-bit pack of the
+    same numbers, so both paths of the module (and a 16-bit module loaded from its state_dict) compute the same thing."""
 
     def __init__(self, in_features, out_features, bias=True, ops=None):
         super().__init__(in_features, out_features, bias=bias)
         self.ops = ops
         self._packed = {}
         self._packed_key = None
+        self.weight_quant = None
+        self.quant_scope = "target"          # "draft" for the projections of the draft layer (set by the owning model)
+        self._q8 = None                      # (q uint8 [N, K], scale fp32 [N]) of the current weight version (GPU only)
+        self._env_scopes = _env_quant_scopes()
+
+    def _key(self):
+        w = self.weight
+        return (w.data_ptr(), w._version, w.dtype, w.device)
+
+    @torch.no_grad()
+    def quantize_weight_(self):
+        """Round the weight to the e4m3 grid with one power-of-two scale per row (quant.py) and write the de-quantised
+        values back into ``.weight``.  On the GPU the bytes and scales are kept for the 8-bit pack."""
+        from . import quant
+        w = self.weight
+        on_gpu = w.is_cuda and hasattr(self.ops, "quantize_rows_e4m3") and w.dtype in (torch.float16, torch.bfloat16) \
+            and self.in_features % 8 == 0
+        q, scale = self.ops.quantize_rows_e4m3(w) if on_gpu else quant.quantize_rows_e4m3(w)
+        w.copy_(quant.dequantize_rows_e4m3(q, scale, w.dtype))
+        self._q8 = (q, scale) if on_gpu else None
+        self.weight_quant = "fp8"
+        self._packed = {}
+        self._packed_key = self._key()
+        return self
+
+    def _quant_due(self) -> bool:
+        """The weight is (to be) kept on the e4m3 grid and has changed since it was last rounded.  The process-wide default
+        (LONGSPEC_WEIGHT_QUANT) is honoured here, at the first use, because a benchmark may fill the weights in place after
+        constructing the model."""
+        return (self.weight_quant is not None or self.quant_scope in self._env_scopes) and self._packed_key != self._key()
 
     def packed(self, rope: bool = False):
         """The streamed copy of the weight; ``rope=True``: the q/k layout of ``ops.linear_qkv_rope``."""
-        w = self.weight
-        key = (w.data_ptr(), w._version, w.dtype, w.device)
+        key = self._key()
         if self._packed_key != key:
-            self._packed = {}
-            self._packed_key = key
+            if self._quant_due():
+                self.quantize_weight_()
+            else:
+                self._packed, self._packed_key = {}, key
         if rope not in self._packed:
-            self._packed[rope] = self.ops.pack_weight(w, rope=True) if rope else self.ops.pack_weight(w)
+            if self.weight_quant is not None:
+                if self._q8 is None:
+                    raise RuntimeError("DecodeLinear: an fp8 weight streams through the HIP operator layer only (fp16 / bf16 on the GPU)")
+                self._packed[rope] = self.ops.pack_weight8(self._q8, rope=rope)
+            else:
+                self._packed[rope] = self.ops.pack_weight(self.weight, rope=True) if rope else self.ops.pack_weight(self.weight)
         return self._packed[rope]
 
     def streams(self, x) -> bool:
@@ -110,6 +162,8 @@ class DecodeLinear(nn.Linear):
         """``residual``: returns ``residual + linear(x)`` (one launch when the input is decode-shaped)."""
         if self.streams(x):
             return self.ops.linear(x, self.packed(), self.bias, residual=residual)
+        if self._quant_due():
+            self.quantize_weight_()          # prefill multiplies the same (rounded) numbers as the decode passes
         y = F.linear(x, self.weight, self.bias)
         return y if residual is None else residual + y
 
@@ -143,10 +197,17 @@ class LlamaMLP(nn.Module):
         self._gate_up_key = None
 
     def _packed_gate_up(self):
-        g, u = self.gate_proj.weight, self.up_proj.weight
-        key = (g.data_ptr(), g._version, u.data_ptr(), u._version, g.dtype, g.device)
+        gp, up = self.gate_proj, self.up_proj
+        for m in (gp, up):
+            if m._quant_due():
+                m.quantize_weight_()
+        g, u = gp.weight, up.weight
+        key = (g.data_ptr(), g._version, u.data_ptr(), u._version, g.dtype, g.device, gp.weight_quant, up.weight_quant)
         if self._gate_up_key != key:
-            self._gate_up = self.ops.pack_gate_up(g, u)
+            if gp.weight_quant is not None and up.weight_quant is not None:
+                self._gate_up = self.ops.pack_gate_up8(gp._q8, up._q8)
+            else:
+                self._gate_up = self.ops.pack_gate_up(g, u)
             self._gate_up_key = key
         return self._gate_up
 
@@ -456,3 +517,24 @@ class LlamaForCausalLM(nn.Module):
     def set_max_gen_len(self, max_gen_len):                          # llama.py:646-648
         for layer in self.model.layers:
             layer.self_attn.max_len = max_gen_len
+
+    QUANT_SCOPES = {"target": ("target",), "draft": ("draft",), "all": ("draft", "target")}
+
+    @torch.no_grad()
+    def quantize_weights_(self, scope: str = "all"):
+        """FP8 (e4m3) weights for the decode projections (no counterpart in the reference).  ``scope``: ``"target"`` (the
+        decoder layers' q/k/v/o and MLP projections and the lm_head -- which the draft passes share), ``"draft"`` (the
+        projections of the draft layer; lossless with respect to the 16-bit target, which still verifies every token) or
+        ``"all"``.  Embeddings and norms are never quantised.
+
+        Every projection in scope has its weight rounded to the e4m3 grid with a power-of-two scale per output row
+        (``quant.py``); the de-quantised values -- exact in fp16 / bf16 -- are written back into ``.weight`` and, on the
+        GPU, the decode-shaped path streams the 8-bit pack.  Prefill-shaped calls keep multiplying ``.weight``, and so does
+        the vocabulary-sharded lm_head slice (``dist.KVShard.head_select``), which stays 16-bit: the same numbers.  The model
+        is therefore the 16-bit model with these weights, token for token.  On the CPU only ``.weight`` is rewritten."""
+        if scope not in self.QUANT_SCOPES:
+            raise ValueError(f"quantize_weights_: scope {scope!r} is not one of {sorted(self.QUANT_SCOPES)}")
+        for m in self.modules():
+            if isinstance(m, DecodeLinear) and m.quant_scope in self.QUANT_SCOPES[scope]:
+                m.quantize_weight_()
+        return self

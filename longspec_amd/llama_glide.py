@@ -200,6 +200,9 @@ class LlamaGlide(LlamaForCausalLM):
     def __init__(self, config, target_model_path=None, glide_path=None, ops=None, dtype=torch.float16, device=None):
         super().__init__(config, ops=ops)
         self.glide = self.GLIDE_LAYER_CLS(config, ops=self.ops)
+        for m in self.glide.modules():
+            if isinstance(m, DecodeLinear):
+                m.quant_scope = "draft"        # quantize_weights_("draft") / LONGSPEC_WEIGHT_QUANT=fp8-draft
         if target_model_path is not None or glide_path is not None:
             from .checkpoint import load_draft_checkpoint, load_target_checkpoint
             if target_model_path is not None:

@@ -12,6 +12,7 @@ One function per reference seam of the draft-then-verify round:
   logprob_topk / argmax_rows   beam growth and greedy verification on the lm_head logits  llama_glide.py:1019-1064,1091
   linear / linear_multi / mlp_gate_up   the projections of a decode pass (M <= 80 token rows):
                          q/k/v/o_proj llama.py:361-363,390, LlamaMLP (qwen2.py:218-230), lm_head llama_glide.py:1091
+                         -- with 16-bit (pack_weight) or 8-bit e4m3 (pack_weight8) packed weights
 
 Everything runs on the CURRENT torch stream, without host synchronisation.  There is
 no fallback: a missing extension or a CPU tensor raises.
@@ -154,6 +155,72 @@ def pack_gate_up(gate_weight: torch.Tensor, up_weight: torch.Tensor) -> PackedWe
     return PackedWeight(out, N, K)
 
 
+class PackedWeight8:
+    """A weight [N, K] as OCP e4m3fn bytes in the streamed 8-bit layout (``ls_linear_w8_pack``, include/longspec_hip.h)
+    plus one fp32 scale per row: ``W[n, k] = q[n, k] * scale[n]``.  ``data`` is a flat uint8 tensor of ceil(N/64)*64*K
+    bytes; ``scale`` is [N] (a gate/up pair: [2, N], gate rows first).  ``dtype`` is always ``torch.uint8``: the
+    activation dtype is the caller's."""
+    __slots__ = ("data", "scale", "n", "k", "dtype", "rope", "pair")
+
+    def __init__(self, data, scale, n, k, rope=False, pair=False):
+        self.data, self.scale, self.n, self.k, self.dtype, self.rope, self.pair = data, scale, n, k, torch.uint8, rope, pair
+
+
+W8_CALLS = 0          # launches of ls_linear_w8_fwd so far (tests assert that a quantised model really streams 8-bit weights)
+
+
+def quantize_rows_e4m3(weight: torch.Tensor, pow2: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Device twin of ``quant.quantize_rows_e4m3`` (bit-identical): fp16 / bf16 [N, K] -> (q uint8 [N, K], scale fp32 [N])."""
+    _dev(weight)
+    if weight.dim() != 2 or weight.shape[1] % 8 != 0:
+        raise ValueError("quantize_rows_e4m3: [N, K] weight with K a multiple of 8 expected")
+    w = weight.detach().contiguous()
+    N, K = w.shape
+    q = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    scale = torch.empty((N,), dtype=torch.float32, device=w.device)
+    _C.check(_C.load().ls_linear_w8_quantize(w.data_ptr(), N, K, _dtype(w), int(bool(pow2)), q.data_ptr(), scale.data_ptr(), _stream()),
+             "ls_linear_w8_quantize")
+    return q, scale
+
+
+def _as_q_scale(weight):
+    """``weight``: a 16-bit [N, K] tensor (quantised here, power-of-two scales) or a pre-quantised ``(q uint8 [N, K],
+    scale fp32 [N])`` pair (any positive scales: a checkpoint quantised elsewhere)."""
+    if isinstance(weight, (tuple, list)):
+        q, scale = weight
+        _dev(q, scale)
+        if q.dtype != torch.uint8 or q.dim() != 2 or scale.numel() != q.shape[0]:
+            raise ValueError("pack_weight8: a pre-quantised weight is (q uint8 [N, K], scale [N])")
+        return q.contiguous(), scale.detach().to(torch.float32).reshape(-1).contiguous()
+    return quantize_rows_e4m3(weight)
+
+
+def pack_weight8(weight, rope: bool = False) -> PackedWeight8:
+    """Quantise (unless ``weight`` is already a ``(q, scale)`` pair) and pack for the 8-bit skinny GEMM.  ``rope=True``:
+    the q/k layout of ``linear_qkv_rope``."""
+    q, scale = _as_q_scale(weight)
+    N, K = q.shape
+    if K % 64 != 0 or K < 128 or (rope and N % 128 != 0):
+        raise ValueError("pack_weight8: K must be a multiple of 64 (>= 128); rope=True needs N = heads x 128")
+    lib = _C.load()
+    out = torch.empty(lib.ls_linear_w8_packed_bytes(N, K), dtype=torch.uint8, device=q.device)
+    _C.check(lib.ls_linear_w8_pack(q.data_ptr(), None, out.data_ptr(), N, K, int(rope), _stream()), "ls_linear_w8_pack")
+    return PackedWeight8(out, scale, N, K, rope=rope)
+
+
+def pack_gate_up8(gate_weight, up_weight) -> PackedWeight8:
+    """gate_proj / up_proj of one MLP (16-bit tensors or ``(q, scale)`` pairs) as one 8-bit packed matrix with alternating
+    16-row tiles: the operand of ``mlp_gate_up``."""
+    (qg, sg), (qu, su) = _as_q_scale(gate_weight), _as_q_scale(up_weight)
+    if qg.shape != qu.shape or qg.shape[0] % 16 or qg.shape[1] % 64 or qg.shape[1] < 128:
+        raise ValueError("pack_gate_up8: two [N, K] weights with N % 16 == 0 and K % 64 == 0 expected")
+    N, K = qg.shape
+    lib = _C.load()
+    out = torch.empty(lib.ls_linear_w8_packed_bytes(2 * N, K), dtype=torch.uint8, device=qg.device)
+    _C.check(lib.ls_linear_w8_pack(qg.data_ptr(), qu.data_ptr(), out.data_ptr(), N, K, 0, _stream()), "ls_linear_w8_pack")
+    return PackedWeight8(out, torch.stack([sg, su]).contiguous(), N, K, pair=True)
+
+
 def logprob_topk(logits: torch.Tensor, history: Optional[torch.Tensor], k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(logits.float().log_softmax(-1) + history[..., None]).view(bsz, -1).topk(k)`` (llama_glide.py:1019-1020,
     1046-1064) straight from the fp16 lm_head output: logits [bsz, rows, V], history [bsz, rows] fp32 or None ->
@@ -279,11 +346,27 @@ def _linear_call(x, weights, biases, epilogue, n_splits=0, timing=None, rope=Non
     d = _C.LinearDesc()
     d.x = x2.data_ptr()
     n_tot = 0
+    w8 = isinstance(weights[0], PackedWeight8)
+    if w8:
+        if any(not isinstance(w, PackedWeight8) for w in weights):
+            raise ValueError("linear: the segments of one call are all 8-bit or all 16-bit packed weights")
+        if norm is not None or ssq_out:
+            raise ValueError("linear: the folded RMSNorm (norm=, ssq_out=) is not available with 8-bit weights")
+        if weights[0].pair != (epilogue == _C.LS_EPI_SILU_MUL):
+            raise ValueError("linear: mlp_gate_up takes pack_gate_up8(...), every other call pack_weight8(...)")
+        scales = (C.c_void_p * 3)()
     for i, w in enumerate(weights):
-        if not isinstance(w, PackedWeight):
+        if not isinstance(w, (PackedWeight8 if w8 else PackedWeight)):
+            if isinstance(w, PackedWeight8):
+                raise ValueError("linear: the segments of one call are all 8-bit or all 16-bit packed weights")
             raise TypeError("linear: weights must be PackedWeight (ops.pack_weight(nn.Linear.weight))")
-        if w.k != K or w.dtype != x.dtype:
+        if w.k != K or (not w8 and w.dtype != x.dtype):
             raise ValueError(f"packed weight [{w.n}, {w.k}] {w.dtype} does not match x [..., {K}] {x.dtype}")
+        if w8:
+            if w.pair:
+                scales[0], scales[1] = w.scale[0].data_ptr(), w.scale[1].data_ptr()
+            else:
+                scales[i] = w.scale.data_ptr()
         if w.rope != (epilogue == _C.LS_EPI_QKV_ROPE and i < 2):
             raise ValueError("linear: q/k weights of linear_qkv_rope are packed with rope=True, every other weight without")
         d.w[i] = w.data.data_ptr()
@@ -330,19 +413,26 @@ def _linear_call(x, weights, biases, epilogue, n_splits=0, timing=None, rope=Non
         d.ssq_out = ssq.data_ptr()
     if timing is None and _linear_timing is not None:
         rows_w = sum(w.n for w in weights) * (2 if epilogue == _C.LS_EPI_SILU_MUL else 1)
-        timing = _linear_timing((rows_w * K + M * K + M * n_out) * x.element_size())
+        timing = _linear_timing(rows_w * K * (1 if w8 else x.element_size()) + (M * K + M * n_out) * x.element_size())
     if timing is not None:          # (torch.cuda.Event, torch.cuda.Event), both already created by a record()
         d.ev_start, d.ev_stop = timing[0].cuda_event, timing[1].cuda_event
     lib = _C.load()
-    key = (M, K, d.n[0], d.n[1], d.n[2], epilogue, n_splits, d.dtype, norm is not None)
+    key = (M, K, d.n[0], d.n[1], d.n[2], epilogue, n_splits, d.dtype, norm is not None, w8)
     need = _linear_need.get(key)
     if need is None:
-        need = lib.ls_linear_workspace_bytes(C.byref(d))
-        if need == 0:
-            _C.check(lib.ls_linear_fwd(C.byref(d), None, 0, _stream()), "ls_linear_fwd")      # raises with the reason
+        need = lib.ls_linear_w8_workspace_bytes(C.byref(d)) if w8 else lib.ls_linear_workspace_bytes(C.byref(d))
+        if need == 0:                                                                          # raises with the reason
+            if w8:
+                _C.check(lib.ls_linear_w8_fwd(C.byref(d), scales, None, 0, _stream()), "ls_linear_w8_fwd")
+            _C.check(lib.ls_linear_fwd(C.byref(d), None, 0, _stream()), "ls_linear_fwd")
         _linear_need[key] = need
     stream = _stream()
     ws = _gemm_ws.get(x.device, need, stream)
+    if w8:
+        global W8_CALLS
+        _C.check(lib.ls_linear_w8_fwd(C.byref(d), scales, ws.data_ptr(), ws.numel(), stream), "ls_linear_w8_fwd")
+        W8_CALLS += 1
+        return y
     if PREFETCH_PROBE > 0:          # tools/bench_l2_prefetch.py: what an L2-resident head of the weight stream is worth
         ev = (d.ev_start, d.ev_stop)
         d.ev_start, d.ev_stop = None, None
