@@ -21,7 +21,7 @@
 // number of ranks (stage 1 of a chunk never depended on the other chunks).
 //
 // Ties (equal fp32 values; fp16 logits collide often) go to the smaller flat index row * V + column, which
-// is also what `argmax` returns in PyTorch.  Latency-bound (256 KB .. 18 MB of L2-resident logits):
+// is also what `argmax` returns in PyTorch.  -0.0 and +0.0 are equal logits: stage 1 gives them one key.  Latency-bound (256 KB .. 18 MB of L2-resident logits):
 // reported in microseconds, not against a roofline.
 #include "ls_common.h"
 
@@ -38,8 +38,11 @@ __device__ __forceinline__ float* ws_rec(float* ws, int row, int slot, int rows,
     return ws + ((long)slot * rows + row) * (2 + 2 * k);
 }
 
-// 16-bit float pattern -> unsigned key that orders like the value (no NaNs on this path)
-__device__ __forceinline__ unsigned order_key(unsigned bits16) { return (bits16 & 0x8000u) ? (~bits16 & 0xffffu) : (bits16 | 0x8000u); }
+// 16-bit float pattern -> unsigned key that orders like the value (no NaNs on this path): 0x8000 plus or minus the
+// magnitude bits, so that -0.0 and +0.0, equal as floats, share the key 0x8000 and the column decides between them
+__device__ __forceinline__ unsigned order_key(unsigned bits16) {
+    return (bits16 & 0x8000u) ? 0x8000u - (bits16 & 0x7fffu) : (bits16 | 0x8000u);
+}
 
 // wave-wide max / min of a 32-bit unsigned through the DPP network (6 VALU pairs, no LDS crossbar): quad swaps,
 // row rotations, then row broadcasts; every lane of the result's last row holds ... lane 63 holds the total.

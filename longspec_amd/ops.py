@@ -228,7 +228,8 @@ def logprob_topk(logits: torch.Tensor, history: Optional[torch.Tensor], k: int) 
     _dev(logits, history)
     if logits.dim() == 2:
         logits = logits.unsqueeze(1)
-    if logits.stride(-1) != 1 or logits.stride(1) % 8 != 0:
+    if (logits.stride(-1) != 1 or logits.stride(1) % 8 != 0 or (logits.shape[0] > 1 and logits.stride(0) % 8 != 0)
+            or logits.data_ptr() % 16 != 0):                           # the kernel loads 16 bytes at a time
         logits = logits.contiguous()
     b, R, V = logits.shape
     if k > 64 or R > 128 or R * ((V + 8191) // 8192) * k > 5120 or R * ((V + 8191) // 8192) > 512 or V % 8:
@@ -257,7 +258,7 @@ def argmax_rows(logits: torch.Tensor) -> torch.Tensor:
     shape = logits.shape[:-1]
     V = logits.shape[-1]
     x = logits.reshape(-1, V)
-    if x.stride(-1) != 1 or x.stride(0) % 8 != 0:
+    if x.stride(-1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
         x = x.contiguous()
     out = torch.empty((x.shape[0],), dtype=torch.int64, device=logits.device)
     lib = _C.load()
