@@ -1668,15 +1668,21 @@ __global__ void pack_mask_kernel(const int64_t* mask, int M, int N, uint32_t* bi
 }
 
 // ---- host side ---------------------------------------------------------------------------
+// What a launch needs is decided once per descriptor, by plan_attn(); every entry point asks it and nothing else, so the
+// three calls of the sharded path (partial -> reduce_push -> finish_xchg) cannot derive different plans.
+constexpr int TILE = 64;            // keys per LDS tile of the general kernel (AttnK::tile)
+constexpr int LONG_PREFIX = 4096;   // kv_len_hint from which a prefix counts as long
+
+// The six stage-1 instantiations per dtype: attn_partial_kernel<E, QTA, QTB> and attn_partial_ws_kernel<E, WS_QT or 3>
+enum Stage1 { GEN_1_1, GEN_2_2, GEN_3_2, GEN_3_3, WS_FULL, WS_3 };
+
 struct Cfg {
-    int qtA, qtB, rbA, RB, KS, tile, bpw, nstages, nd, pp, row_chunks, rows_per_chunk, threads, lds;
-    bool ws;       // warp-specialised prefix path (attn_partial_ws_kernel)
-    int ws_qt;     // row tiles per S/O pair of the warp-specialised kernel
+    Stage1 kern;
+    int row_chunks, RB, KS, rbA, qtA, qtB;                              // chosen per launch class
+    int bpw, nd, pp, rows_per_chunk, nstages, threads, lds;             // derived from those
+    bool ws() const { return kern >= WS_FULL; }                         // warp-specialised prefix path
 };
 
-// Workgroup shape for M = g*sq rows sharing one K/V stream (see the header comment).
-// The warp-specialised kernel takes the verification-sized row blocks (17..20 tiles) of calls whose prefix has
-// no causal / window edge (every row sees keys [0, L)) and whose new block fits its smaller ring.
 // Which streaming kernel serves verification-sized row blocks: LS_ATTN_KERNEL = ws (default) | general, read ONCE per
 // process (A/B switch of the benchmarks).  True: the warp-specialised kernel is enabled.
 bool ws_kernel_enabled() {
@@ -1687,59 +1693,49 @@ bool ws_kernel_enabled() {
     return enabled;
 }
 
-bool ws_eligible(const ls_attn_desc* d) {
+// The warp-specialised kernel takes the verification-sized row blocks (17..20 tiles) of calls whose prefix has
+// no causal / window edge (every row sees keys [0, L)) and whose new block fits its smaller ring.
+bool ws_eligible(const ls_attn_desc* d, bool long_prefix) {
     if (!ws_kernel_enabled()) return false;
     // causal with ALL query rows appended (the chunks of a long prompt, ops._prefill_attention_batched): the diagonal lives
     // in the new-key block and every row sees the whole prefix -- hi(r) = min(L, r + sk - sq + 1) = L when sk = L + sq.
     // Only for long prompts: short ones keep the kernel (and the rounding) the goldens were generated against.
-    const bool append_chunk = d->causal != 0 && d->new_mode == LS_NEW_FLASH && d->n_app == d->sq && d->kv_len_hint >= 4096;
+    const bool append_chunk = d->causal != 0 && d->new_mode == LS_NEW_FLASH && d->n_app == d->sq && long_prefix;
     return (d->causal == 0 || append_chunk) && d->window_left < 0 &&
            (d->new_mode == LS_NEW_NONE || d->n_new <= WS_NEW_CAP / 64 * 64);
 }
 
+// Workgroup shape for M = g*sq rows sharing one K/V stream (see the header comment), one line per launch class, named by its
+// row tiles of 16 as tests/test_gpu_attn_dispatch.py names them: RB row blocks x KS key slices, blocks 0..rbA-1 of qtA tiles,
+// the others of qtB.  "Nx20" (g*sq > 384 rows): N row chunks re-read the K/V stream.
+// 21..24 row tiles (GQA-5 x 74 verification rows = 370: QwQ) run as TWO row chunks of 12 tiles on the warp-specialised
+// kernel with 3 tiles per S/O pair (new-key block: 4 workers x 3 tiles per chunk): six tiles per pair do not fit the S wave's
+// registers (96 for Q^T alone), and the general kernel that served this shape until round 3 ran it at 0.23 of the HBM
+// roofline.  The chunks re-read the K/V stream (from L2: the two workgroups of a split run side by side); half as many
+// splits, the same partial volume.  Long prefixes only: short ones keep the kernel (and the roundings) the bf16 golden runs
+// were generated against -- a fixed soft-max reference and bf16 row sums moved one token of `qwen_bf16_g5`
+// (tests/test_gpu_generate.py).
 Cfg pick_cfg(int M, bool ws_ok, bool long_prefix) {
+    const int tiles = (M + 15) / 16, pairs = (tiles + 1) / 2;
+    const Stage1 wide = ws_ok ? WS_FULL : GEN_3_2;      // 20 tiles dealt 3,3,3,3,2,2,2,2
     Cfg c;
-    c.ws = false;
-    c.ws_qt = WS_QT;
-    int tiles = (M + 15) / 16;
-    c.row_chunks = 1;
-    if (tiles > 24) {                   // g*sq > 384 rows: several row chunks re-read the K/V stream
-        c.row_chunks = (M + 319) / 320;
-        tiles = 20;
-    }
-    const bool ws2 = ws_ok && long_prefix && tiles > 20 && tiles <= 24;
-    // 21..24 row tiles (GQA-5 x 74 verification rows = 370: QwQ) run as TWO row chunks of 12 tiles on the warp-specialised
-    // kernel with 3 tiles per S/O pair: six tiles per pair do not fit the S wave's registers (96 for Q^T alone), and the general
-    // kernel that served this shape until round 3 ran it at 0.23 of the HBM roofline.  The chunks re-read the K/V stream (from
-    // L2: the two workgroups of a split run side by side); half as many splits, the same partial volume.  Prefixes of 4096 rows
-    // and more only: short ones keep the kernel (and the roundings) the bf16 golden runs were generated against -- a fixed
-    // soft-max reference and bf16 row sums moved one token of `qwen_bf16_g5` (tests/test_gpu_generate.py).
-    if (tiles <= 1) { c.qtA = c.qtB = 1; c.RB = 1; c.KS = 2; }
-    else if (tiles <= 8) { c.qtA = c.qtB = 2; c.RB = (tiles + 1) / 2; c.KS = 2; }
-    else if (tiles <= 16) { c.qtA = c.qtB = 2; c.RB = (tiles + 1) / 2; c.KS = 1; }
-    else if (tiles <= 20) { c.qtA = 3; c.qtB = 2; c.RB = 8; c.KS = 1; }      // 3,3,3,3,2,2,2,2
-    else { c.qtA = c.qtB = 3; c.RB = 8; c.KS = 1; }
-    if (ws2) { c.row_chunks = 2; c.qtA = c.qtB = 3; c.RB = 4; c.KS = 1; }      // new-key block: 4 workers x 3 tiles per chunk
-    c.rbA = c.qtA == c.qtB ? c.RB : 4;
-    c.bpw = c.KS == 1 ? 2 : 1;          // 32-key blocks per wave and tile
-    c.tile = 64;
-    c.nstages = 4;                      // 128 KB LDS ring; 2 tiles (64 KB) in flight beside the 2 being read
-    const int nw = ws2 ? 8 : c.RB * c.KS;
-    c.nd = nw >= 8 ? 8 : (nw >= 4 ? 4 : (nw >= 2 ? 2 : 1));
-    c.pp = (c.tile / 2) / c.nd;         // pieces (1 KB) per DMA wave and tile
+    //                                                    kernel   chunks           RB     KS rbA    qtA qtB
+    if (tiles <= 1)                               c = Cfg{GEN_1_1, 1,               1,     2, 1,     1,  1};    // "1"
+    else if (tiles <= 8)                          c = Cfg{GEN_2_2, 1,               pairs, 2, pairs, 2,  2};    // "2-8"
+    else if (tiles <= 16)                         c = Cfg{GEN_2_2, 1,               pairs, 1, pairs, 2,  2};    // "9-16"
+    else if (tiles <= 20)                         c = Cfg{wide,    1,               8,     1, 4,     3,  2};    // "17-20"
+    else if (tiles <= 24 && ws_ok && long_prefix) c = Cfg{WS_3,    2,               4,     1, 4,     3,  3};    // "21-24", long
+    else if (tiles <= 24)                         c = Cfg{GEN_3_3, 1,               8,     1, 8,     3,  3};    // "21-24"
+    else                                          c = Cfg{wide,    (M + 319) / 320, 8,     1, 4,     3,  2};    // "Nx20"
+    const int nw = c.ws() ? 8 : c.RB * c.KS;        // waves; the warp-specialised kernel always runs its 4 S/O pairs
+    c.bpw = c.KS == 1 ? 2 : 1;                      // 32-key blocks per wave and tile
+    c.nd = nw >= 8 ? 8 : (nw >= 4 ? 4 : 2);         // DMA waves
+    c.pp = (TILE / 2) / c.nd;                       // pieces (1 KB) per DMA wave and tile
     c.rows_per_chunk = (c.rbA * c.qtA + (c.RB - c.rbA) * c.qtB) * 16;
     c.threads = nw * 64;
-    c.lds = c.nstages * 2 * c.tile * ROWB + 16;
-    if (ws2) {
-        c.ws = true;
-        c.ws_qt = 3;
-        c.nstages = WS_NEW_CAP / c.tile;
-        c.lds = WS_LDS;
-    } else if (ws_ok && tiles > 16 && tiles <= 20) {       // row split of the new-key block stays 3,3,3,3,2,2,2,2
-        c.ws = true;
-        c.nstages = WS_NEW_CAP / c.tile;            // the new-block workgroup's capacity in the smaller ring
-        c.lds = WS_LDS;
-    }
+    // 128 KB LDS ring: 2 tiles (64 KB) in flight beside the 2 being read; or the new-block workgroup's capacity in the smaller ring
+    c.nstages = c.ws() ? WS_NEW_CAP / TILE : 4;
+    c.lds = c.ws() ? WS_LDS : 4 * 2 * TILE * ROWB + 16;
     return c;
 }
 
@@ -1757,10 +1753,9 @@ int num_cus() {
 
 int pick_splits(const ls_attn_desc* d, const Cfg& c) {
     if (d->n_splits > 0) return d->n_splits;
-    const int tile = c.tile;
     int span = d->kv_len_hint;
     if (d->window_left >= 0) span = span < d->window_left + d->sq + 1 ? span : d->window_left + d->sq + 1;
-    int tiles = (span + tile - 1) / tile + (d->window_left >= 0 ? 1 : 0);
+    int tiles = (span + TILE - 1) / TILE + (d->window_left >= 0 ? 1 : 0);
     if (tiles < 1) tiles = 1;
     const int wg_per_split = d->Hkv * c.row_chunks * d->b;
     // one workgroup per CU in total: the new-block workgroups (one per kv head) count too, otherwise the
@@ -1777,36 +1772,13 @@ int pick_splits(const ls_attn_desc* d, const Cfg& c) {
     // 32-key blocks from the hinted length; the general one: ceil(tiles / s) tiles), only for calls WITHOUT a new-key block,
     // and never below half the target (tiles = 16, s = 2 used to collapse to one split).
     if (d->new_mode == LS_NEW_NONE) {
-        const int unit = c.ws ? 32 : tile;
+        const int unit = c.ws() ? 32 : TILE;
         const int units = (span + unit - 1) / unit;
         int t = s;
         while (t > 1 && units > t && (((units + t - 1) / t) * unit) % 512 == 0) --t;
         if (2 * t >= s) s = t;
     }
     return s;
-}
-
-struct WsLayout {
-    size_t parts_o, parts_lse, new_o, new_lse, total;
-    int n_parts;
-};
-
-WsLayout ws_layout(const ls_attn_desc* d, const Cfg& c, int n_splits) {
-    WsLayout w;
-    w.n_parts = n_splits * c.KS;
-    const size_t rows = (size_t)d->b * d->sq * d->H;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    w.parts_o = take((size_t)w.n_parts * rows * D * 4);
-    w.parts_lse = take((size_t)w.n_parts * rows * 4);
-    w.new_o = take(rows * D * 4);
-    w.new_lse = take(rows * 4);
-    w.total = off;
-    return w;
 }
 
 int validate(const ls_attn_desc* d) {
@@ -1829,45 +1801,55 @@ int validate(const ls_attn_desc* d) {
     return LS_OK;
 }
 
-template <typename E, int QTA, int QTB>
-int launch_partial(const Cfg& c, const AttnK& k, dim3 grid, hipStream_t s) {
-    auto fn = attn_partial_kernel<E, QTA, QTB>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)attr;                     // function-local static: initialised once, thread-safe
-    hipLaunchKernelGGL(fn, grid, dim3(c.threads), c.lds, s, k);
-    LS_CHECK_LAUNCH("attn_partial_kernel");
-    return LS_OK;
-}
+struct WsView {
+    float *parts_o, *parts_lse, *new_o, *new_lse;
+};
 
-template <typename E, int QT>
-int launch_partial_ws(const Cfg& c, const AttnK& k, dim3 grid, hipStream_t s) {
-    auto fn = attn_partial_ws_kernel<E, QT>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)attr;
-    hipLaunchKernelGGL(fn, grid, dim3(c.threads), c.lds, s, k);
-    LS_CHECK_LAUNCH("attn_partial_ws_kernel");
-    return LS_OK;
-}
+struct AttnPlan {
+    Cfg c;                      // stage-1 kernel, c.threads threads, c.lds bytes of LDS
+    int n_splits, n_parts;      // key splits of the prefix; partials per query row = n_splits * KS
+    dim3 grid;                  // (key splits + the new-key workgroup, kv heads x row chunks, batch)
+    size_t parts_o, parts_lse, new_o, new_lse, ws_bytes;    // workspace: byte offsets of its four blocks, and its size
+    WsView ws;                  // the four blocks in the caller's workspace: null until ws_view() has checked it
+};
 
-template <typename E>
-int dispatch_partial(const Cfg& c, const AttnK& k, dim3 grid, hipStream_t s) {
-    if (c.ws) return c.ws_qt == 3 ? launch_partial_ws<E, 3>(c, k, grid, s) : launch_partial_ws<E, WS_QT>(c, k, grid, s);
-    if (c.qtA == 1) return launch_partial<E, 1, 1>(c, k, grid, s);
-    if (c.qtA == 2) return launch_partial<E, 2, 2>(c, k, grid, s);
-    if (c.qtB == 2) return launch_partial<E, 3, 2>(c, k, grid, s);
-    return launch_partial<E, 3, 3>(c, k, grid, s);
-}
+size_t pad256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
-int run_partial(const ls_attn_desc* d, void* ws, size_t ws_bytes, hipStream_t s, WsLayout* out_layout) {
-    int rc = validate(d);
+// Validates `d` (LS_ERR_* + message) and fills `p`.  Pure host arithmetic: nothing is launched or allocated.
+int plan_attn(const ls_attn_desc* d, AttnPlan* p) {
+    const int rc = validate(d);
     if (rc) return rc;
-    const int g = d->H / d->Hkv;
-    const Cfg c = pick_cfg(g * d->sq, ws_eligible(d), d->kv_len_hint >= 4096);
-    const int n_splits = pick_splits(d, c);
-    const WsLayout w = ws_layout(d, c, n_splits);
-    if (!ws || ws_bytes < w.total) LS_FAIL(LS_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, w.total);
+    const bool long_prefix = d->kv_len_hint >= LONG_PREFIX;
+    p->c = pick_cfg(d->H / d->Hkv * d->sq, ws_eligible(d, long_prefix), long_prefix);
+    p->n_splits = pick_splits(d, p->c);
+    p->n_parts = p->n_splits * p->c.KS;
+    p->grid = dim3(p->n_splits + (d->new_mode != LS_NEW_NONE), d->Hkv * p->c.row_chunks, d->b);
+    const size_t rows = (size_t)d->b * d->sq * d->H;
+    p->parts_o = 0;
+    p->parts_lse = p->parts_o + pad256((size_t)p->n_parts * rows * D * 4);
+    p->new_o = p->parts_lse + pad256((size_t)p->n_parts * rows * 4);
+    p->new_lse = p->new_o + pad256(rows * D * 4);
+    p->ws_bytes = p->new_lse + pad256(rows * 4);
+    p->ws = WsView{};
+    return LS_OK;
+}
+
+// The four blocks of the caller's workspace, or LS_ERR_WORKSPACE; none asked for and none given if `need` is false (a finish
+// without a new-key block reads nothing from it).
+int ws_view(AttnPlan* p, void* ws, size_t ws_bytes, bool need) {
+    if (!need) return LS_OK;
+    if (!ws || ws_bytes < p->ws_bytes) LS_FAIL(LS_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, p->ws_bytes);
+    char* base = static_cast<char*>(ws);
+    p->ws.parts_o = reinterpret_cast<float*>(base + p->parts_o);
+    p->ws.parts_lse = reinterpret_cast<float*>(base + p->parts_lse);
+    p->ws.new_o = reinterpret_cast<float*>(base + p->new_o);
+    p->ws.new_lse = reinterpret_cast<float*>(base + p->new_lse);
+    return LS_OK;
+}
+
+AttnK attn_args(const ls_attn_desc* d, const AttnPlan& p) {
+    const Cfg& c = p.c;
+    const WsView& v = p.ws;
     AttnK k;
     k.q = d->q;
     k.k_cache = d->k_cache;
@@ -1878,12 +1860,11 @@ int run_partial(const ls_attn_desc* d, void* ws, size_t ws_bytes, hipStream_t s,
     k.v_new = d->v_new;
     k.cache_seqlens = d->cache_seqlens;
     k.mask_bits = d->mask_bits;
-    char* base = static_cast<char*>(ws);
-    k.parts_o = reinterpret_cast<float*>(base + w.parts_o);
-    k.parts_lse = reinterpret_cast<float*>(base + w.parts_lse);
-    k.new_o = reinterpret_cast<float*>(base + w.new_o);
-    k.new_lse = reinterpret_cast<float*>(base + w.new_lse);
-    k.b = d->b; k.sq = d->sq; k.H = d->H; k.Hkv = d->Hkv; k.g = g; k.M = g * d->sq;
+    k.parts_o = v.parts_o;
+    k.parts_lse = v.parts_lse;
+    k.new_o = v.new_o;
+    k.new_lse = v.new_lse;
+    k.b = d->b; k.sq = d->sq; k.H = d->H; k.Hkv = d->Hkv; k.g = d->H / d->Hkv; k.M = k.g * d->sq;
     k.has_new = d->new_mode != LS_NEW_NONE;
     k.new_mode = d->new_mode;
     k.n_new = d->n_new;
@@ -1894,61 +1875,100 @@ int run_partial(const ls_attn_desc* d, void* ws, size_t ws_bytes, hipStream_t s,
     k.causal = d->causal;
     k.window_left = d->window_left;
     k.n_app = d->n_app;
-    k.n_splits = n_splits;
+    k.n_splits = p.n_splits;
     k.row_chunks = c.row_chunks;
     k.rows_per_chunk = c.rows_per_chunk;
-    k.RB = c.RB; k.KS = c.KS; k.tile = c.tile; k.bpw = c.bpw; k.nstages = c.nstages; k.nd = c.nd; k.pp = c.pp;
+    k.RB = c.RB; k.KS = c.KS; k.tile = TILE; k.bpw = c.bpw; k.nstages = c.nstages; k.nd = c.nd; k.pp = c.pp;
     k.rbA = c.rbA; k.qtA = c.qtA; k.qtB = c.qtB;
     k.pp_extra = 0;
     k.scale = d->softmax_scale;
     k.q_sb = d->q_stride_b; k.q_ss = d->q_stride_s; k.q_sh = d->q_stride_h;
     k.kc_sb = d->kc_stride_b; k.kc_ss = d->kc_stride_s; k.kc_sh = d->kc_stride_h;
     k.kn_sb = d->kn_stride_b; k.kn_ss = d->kn_stride_s; k.kn_sh = d->kn_stride_h;
-    dim3 grid(n_splits + k.has_new, d->Hkv * c.row_chunks, d->b);
+    return k;
+}
+
+const char* stage1_name(const Cfg& c) { return c.ws() ? "attn_partial_ws_kernel" : "attn_partial_kernel"; }
+
+template <void (*FN)(const AttnK)>
+int launch_partial(const AttnPlan& p, const AttnK& k, hipStream_t s) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(FN),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)attr;                     // function-local static: initialised once per instantiation, thread-safe
+    hipLaunchKernelGGL(FN, p.grid, dim3(p.c.threads), p.c.lds, s, k);
+    LS_CHECK_LAUNCH(stage1_name(p.c));
+    return LS_OK;
+}
+
+template <typename E>
+int dispatch_partial(const AttnPlan& p, const AttnK& k, hipStream_t s) {
+    switch (p.c.kern) {
+    case GEN_1_1: return launch_partial<attn_partial_kernel<E, 1, 1>>(p, k, s);
+    case GEN_2_2: return launch_partial<attn_partial_kernel<E, 2, 2>>(p, k, s);
+    case GEN_3_2: return launch_partial<attn_partial_kernel<E, 3, 2>>(p, k, s);
+    case GEN_3_3: return launch_partial<attn_partial_kernel<E, 3, 3>>(p, k, s);
+    case WS_FULL: return launch_partial<attn_partial_ws_kernel<E, WS_QT>>(p, k, s);
+    default: return launch_partial<attn_partial_ws_kernel<E, 3>>(p, k, s);        // WS_3
+    }
+}
+
+int run_partial(const ls_attn_desc* d, const AttnPlan& p, hipStream_t s) {
+    const AttnK k = attn_args(d, p);
     if (d->ev_start) (void)hipEventRecord(static_cast<hipEvent_t>(d->ev_start), s);
-    rc = d->dtype == LS_F16 ? dispatch_partial<ElemF16>(c, k, grid, s) : dispatch_partial<ElemBF16>(c, k, grid, s);
+    const int rc = d->dtype == LS_F16 ? dispatch_partial<ElemF16>(p, k, s) : dispatch_partial<ElemBF16>(p, k, s);
     if (d->ev_stop) (void)hipEventRecord(static_cast<hipEvent_t>(d->ev_stop), s);
-    if (out_layout) *out_layout = w;
     return rc;
 }
 
-int run_finish(const ls_attn_desc* d, const float* parts_o, const float* parts_lse, int n_parts, const float* new_o,
-               const float* new_lse, int mode, void* out, float* o32, float* lse, hipStream_t s, long part_o_stride = 0,
-               long part_lse_stride = 0, const ls_xchg* x = nullptr, int x_mode = 0) {
-    FinK f;
-    f.x_mode = x ? x_mode : 0;
-    f.x_rank = x ? x->rank : 0;
-    f.x_world = x ? x->world : 0;
-    f.x_cap = x ? (long)x->cap_floats : 0;
-    f.x_lse_off = (long)d->b * d->sq * d->H * D;
-    f.x_peers = x ? x->peers_dev : nullptr;
-    f.x_box = x ? x->box : nullptr;
-    f.x_ctl = x ? x->ctl : nullptr;
-    f.part_o_stride = part_o_stride ? part_o_stride : (long)d->b * d->sq * d->H * D;
-    f.part_lse_stride = part_lse_stride ? part_lse_stride : (long)d->b * d->H * d->sq;
+// Stage-2 arguments over `n_parts` dense partials.  New-key part, outputs and exchange: none, until the caller names them.
+FinK finish_args(const ls_attn_desc* d, const float* parts_o, const float* parts_lse, int n_parts) {
+    FinK f = {};
     f.parts_o = parts_o;
     f.parts_lse = parts_lse;
-    f.new_o = new_o;
-    f.new_lse = new_lse;
-    f.out = out;
-    f.o32 = o32;
-    f.lse_out = lse;
     f.n_parts = n_parts;
+    f.part_o_stride = f.x_lse_off = (long)d->b * d->sq * d->H * D;
+    f.part_lse_stride = (long)d->b * d->H * d->sq;
     f.b = d->b; f.sq = d->sq; f.H = d->H;
-    f.mode = mode;
+    f.mode = LS_NEW_NONE;
     f.out_sb = d->out_stride_b; f.out_ss = d->out_stride_s; f.out_sh = d->out_stride_h;
-    dim3 grid((d->sq + 7) / 8, d->H, d->b);
-    auto launch = [&](auto xm) {
-        constexpr int XM = decltype(xm)::value;
-        if (d->dtype == LS_F16)
-            hipLaunchKernelGGL((attn_finish_kernel<ElemF16, XM>), grid, dim3(256), 0, s, f);
-        else
-            hipLaunchKernelGGL((attn_finish_kernel<ElemBF16, XM>), grid, dim3(256), 0, s, f);
-    };
-    if (f.x_mode == 1) launch(std::integral_constant<int, 1>{});
-    else if (f.x_mode == 2) launch(std::integral_constant<int, 2>{});
-    else launch(std::integral_constant<int, 0>{});
+    return f;
+}
+
+// The finish that ends a call: merges the new-key block, if the call has one, and writes the descriptor's outputs.
+void merge_to_out(FinK& f, const ls_attn_desc* d, const WsView& v) {
+    if (d->new_mode != LS_NEW_NONE) {
+        f.new_o = v.new_o;
+        f.new_lse = v.new_lse;
+    }
+    f.mode = d->new_mode;
+    f.out = d->out;
+    f.lse_out = d->lse;
+}
+
+void use_exchange(FinK& f, const ls_xchg* x, int x_mode) {
+    f.x_mode = x_mode;
+    f.x_rank = x->rank;
+    f.x_world = x->world;
+    f.x_cap = (long)x->cap_floats;
+    f.x_peers = x->peers_dev;
+    f.x_box = x->box;
+    f.x_ctl = x->ctl;
+}
+
+int run_finish(const FinK& f, int dtype, hipStream_t s) {
+    using Kernel = void (*)(const FinK);
+    static const Kernel kernels[2][3] = {       // [dtype][FinK::x_mode]
+        {attn_finish_kernel<ElemF16, 0>, attn_finish_kernel<ElemF16, 1>, attn_finish_kernel<ElemF16, 2>},
+        {attn_finish_kernel<ElemBF16, 0>, attn_finish_kernel<ElemBF16, 1>, attn_finish_kernel<ElemBF16, 2>}};
+    hipLaunchKernelGGL(kernels[dtype != LS_F16][f.x_mode], dim3((f.sq + 7) / 8, f.H, f.b), dim3(256), 0, s, f);
     LS_CHECK_LAUNCH("attn_finish_kernel");
+    return LS_OK;
+}
+
+int xchg_fits(const ls_attn_desc* d, const ls_xchg* x) {
+    if (!x || !x->connected) LS_FAIL(LS_ERR_INVALID_ARG, "exchange object null or not connected");
+    const size_t rec = (size_t)d->b * d->sq * d->H * (D + 1);
+    if (rec > x->cap_floats) LS_FAIL(LS_ERR_INVALID_ARG, "record of %zu floats exceeds the mailbox slot (%zu)", rec, x->cap_floats);
     return LS_OK;
 }
 
@@ -1957,21 +1977,18 @@ int run_finish(const ls_attn_desc* d, const float* parts_o, const float* parts_l
 extern "C" {
 
 size_t ls_attn_workspace_bytes(const ls_attn_desc* d) {
-    if (validate(d)) return 0;
-    const Cfg c = pick_cfg(d->H / d->Hkv * d->sq, ws_eligible(d), d->kv_len_hint >= 4096);
-    return ws_layout(d, c, pick_splits(d, c)).total;
+    AttnPlan p;
+    return plan_attn(d, &p) ? 0 : p.ws_bytes;
 }
 
 int ls_attn_num_parts(const ls_attn_desc* d) {
-    if (validate(d)) return LS_ERR_INVALID_ARG;
-    const Cfg c = pick_cfg(d->H / d->Hkv * d->sq, ws_eligible(d), d->kv_len_hint >= 4096);
-    return pick_splits(d, c) * c.KS;
+    AttnPlan p;
+    return plan_attn(d, &p) ? LS_ERR_INVALID_ARG : p.n_parts;
 }
 
 const char* ls_attn_kernel_name(const ls_attn_desc* d) {
-    if (validate(d)) return "invalid";
-    const Cfg c = pick_cfg(d->H / d->Hkv * d->sq, ws_eligible(d), d->kv_len_hint >= 4096);
-    return c.ws ? "attn_partial_ws_kernel" : "attn_partial_kernel";
+    AttnPlan p;
+    return plan_attn(d, &p) ? "invalid" : stage1_name(p.c);
 }
 
 long ls_attn_redo_count(int reset) {
@@ -1987,89 +2004,86 @@ long ls_attn_redo_count(int reset) {
 }
 
 int ls_attn_partial(const ls_attn_desc* d, void* ws, size_t ws_bytes, void* stream) {
-    return run_partial(d, ws, ws_bytes, static_cast<hipStream_t>(stream), nullptr);
+    AttnPlan p;
+    int rc = plan_attn(d, &p);
+    if (rc == LS_OK) rc = ws_view(&p, ws, ws_bytes, true);
+    return rc ? rc : run_partial(d, p, static_cast<hipStream_t>(stream));
 }
 
 int ls_attn_fwd(const ls_attn_desc* d, void* ws, size_t ws_bytes, void* stream) {
-    WsLayout w;
-    int rc = run_partial(d, ws, ws_bytes, static_cast<hipStream_t>(stream), &w);
+    AttnPlan p;
+    int rc = plan_attn(d, &p);
+    if (rc == LS_OK) rc = ws_view(&p, ws, ws_bytes, true);
     if (rc) return rc;
+    // in front of stage 1: a call that cannot be finished launches nothing
     if (!d->out) LS_FAIL(LS_ERR_INVALID_ARG, "out is null");
     if (d->lse && d->new_mode == LS_NEW_TARGET) LS_FAIL(LS_ERR_INVALID_ARG, "no lse output in LS_NEW_TARGET mode");
-    char* base = static_cast<char*>(ws);
-    const bool has_new = d->new_mode != LS_NEW_NONE;
-    return run_finish(d, reinterpret_cast<float*>(base + w.parts_o), reinterpret_cast<float*>(base + w.parts_lse),
-                      w.n_parts, has_new ? reinterpret_cast<float*>(base + w.new_o) : nullptr,
-                      has_new ? reinterpret_cast<float*>(base + w.new_lse) : nullptr, d->new_mode, d->out, nullptr,
-                      d->lse, static_cast<hipStream_t>(stream));
+    rc = run_partial(d, p, static_cast<hipStream_t>(stream));
+    if (rc) return rc;
+    FinK f = finish_args(d, p.ws.parts_o, p.ws.parts_lse, p.n_parts);
+    merge_to_out(f, d, p.ws);
+    return run_finish(f, d->dtype, static_cast<hipStream_t>(stream));
 }
 
 int ls_attn_reduce_local(const ls_attn_desc* d, void* ws, size_t ws_bytes, float* o32, float* lse, void* stream) {
-    if (validate(d)) return LS_ERR_INVALID_ARG;
+    AttnPlan p;
+    if (plan_attn(d, &p)) return LS_ERR_INVALID_ARG;
     if (!o32 || !lse) LS_FAIL(LS_ERR_INVALID_ARG, "o32/lse null");
-    const Cfg c = pick_cfg(d->H / d->Hkv * d->sq, ws_eligible(d), d->kv_len_hint >= 4096);
-    const WsLayout w = ws_layout(d, c, pick_splits(d, c));
-    if (!ws || ws_bytes < w.total) LS_FAIL(LS_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, w.total);
-    char* base = static_cast<char*>(ws);
-    return run_finish(d, reinterpret_cast<float*>(base + w.parts_o), reinterpret_cast<float*>(base + w.parts_lse),
-                      w.n_parts, nullptr, nullptr, LS_NEW_NONE, nullptr, o32, lse, static_cast<hipStream_t>(stream));
+    if (ws_view(&p, ws, ws_bytes, true)) return LS_ERR_WORKSPACE;
+    FinK f = finish_args(d, p.ws.parts_o, p.ws.parts_lse, p.n_parts);
+    f.o32 = o32;
+    f.lse_out = lse;
+    return run_finish(f, d->dtype, static_cast<hipStream_t>(stream));
 }
 
 int ls_attn_finish(const ls_attn_desc* d, const float* parts_o, const float* parts_lse, int n_parts, int64_t part_o_stride,
                    int64_t part_lse_stride, void* ws, size_t ws_bytes, void* stream) {
-    if (validate(d)) return LS_ERR_INVALID_ARG;
+    AttnPlan p;
+    if (plan_attn(d, &p)) return LS_ERR_INVALID_ARG;
     if (!parts_o || !parts_lse || n_parts < 1 || !d->out) LS_FAIL(LS_ERR_INVALID_ARG, "parts/out null");
-    const Cfg c = pick_cfg(d->H / d->Hkv * d->sq, ws_eligible(d), d->kv_len_hint >= 4096);
-    const WsLayout w = ws_layout(d, c, pick_splits(d, c));
-    const bool has_new = d->new_mode != LS_NEW_NONE;
-    if (has_new && (!ws || ws_bytes < w.total)) LS_FAIL(LS_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, w.total);
-    char* base = static_cast<char*>(ws);
-    return run_finish(d, parts_o, parts_lse, n_parts, has_new ? reinterpret_cast<float*>(base + w.new_o) : nullptr,
-                      has_new ? reinterpret_cast<float*>(base + w.new_lse) : nullptr, d->new_mode, d->out, nullptr,
-                      d->lse, static_cast<hipStream_t>(stream), (long)part_o_stride, (long)part_lse_stride);
-}
-
-static int xchg_fits(const ls_attn_desc* d, const ls_xchg* x) {
-    if (!x || !x->connected) LS_FAIL(LS_ERR_INVALID_ARG, "exchange object null or not connected");
-    const size_t rec = (size_t)d->b * d->sq * d->H * (D + 1);
-    if (rec > x->cap_floats) LS_FAIL(LS_ERR_INVALID_ARG, "record of %zu floats exceeds the mailbox slot (%zu)", rec, x->cap_floats);
-    return LS_OK;
+    if (ws_view(&p, ws, ws_bytes, d->new_mode != LS_NEW_NONE)) return LS_ERR_WORKSPACE;
+    FinK f = finish_args(d, parts_o, parts_lse, n_parts);
+    if (part_o_stride) f.part_o_stride = (long)part_o_stride;           // 0: dense
+    if (part_lse_stride) f.part_lse_stride = (long)part_lse_stride;
+    merge_to_out(f, d, p.ws);
+    return run_finish(f, d->dtype, static_cast<hipStream_t>(stream));
 }
 
 int ls_attn_reduce_push(const ls_attn_desc* d, void* ws, size_t ws_bytes, ls_xchg* x, void* stream) {
-    if (validate(d)) return LS_ERR_INVALID_ARG;
+    AttnPlan p;
+    if (plan_attn(d, &p)) return LS_ERR_INVALID_ARG;
     if (xchg_fits(d, x)) return LS_ERR_INVALID_ARG;
-    const Cfg c = pick_cfg(d->H / d->Hkv * d->sq, ws_eligible(d), d->kv_len_hint >= 4096);
-    const WsLayout w = ws_layout(d, c, pick_splits(d, c));
-    if (!ws || ws_bytes < w.total) LS_FAIL(LS_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, w.total);
-    char* base = static_cast<char*>(ws);
-    return run_finish(d, reinterpret_cast<float*>(base + w.parts_o), reinterpret_cast<float*>(base + w.parts_lse), w.n_parts, nullptr,
-                      nullptr, LS_NEW_NONE, nullptr, nullptr, nullptr, static_cast<hipStream_t>(stream), 0, 0, x, 1);
+    if (ws_view(&p, ws, ws_bytes, true)) return LS_ERR_WORKSPACE;
+    FinK f = finish_args(d, p.ws.parts_o, p.ws.parts_lse, p.n_parts);
+    use_exchange(f, x, 1);
+    return run_finish(f, d->dtype, static_cast<hipStream_t>(stream));
 }
 
 int ls_attn_finish_xchg(const ls_attn_desc* d, ls_xchg* x, void* ws, size_t ws_bytes, void* stream) {
-    if (validate(d)) return LS_ERR_INVALID_ARG;
+    AttnPlan p;
+    if (plan_attn(d, &p)) return LS_ERR_INVALID_ARG;
     if (!d->out) LS_FAIL(LS_ERR_INVALID_ARG, "out null");
     if (xchg_fits(d, x)) return LS_ERR_INVALID_ARG;
-    const Cfg c = pick_cfg(d->H / d->Hkv * d->sq, ws_eligible(d), d->kv_len_hint >= 4096);
-    const WsLayout w = ws_layout(d, c, pick_splits(d, c));
-    const bool has_new = d->new_mode != LS_NEW_NONE;
-    if (has_new && (!ws || ws_bytes < w.total)) LS_FAIL(LS_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, w.total);
-    char* base = static_cast<char*>(ws);
+    if (ws_view(&p, ws, ws_bytes, d->new_mode != LS_NEW_NONE)) return LS_ERR_WORKSPACE;
     // parts = the mailbox slots of this epoch (resolved on the device); stride = one slot
-    return run_finish(d, nullptr, nullptr, x->world, has_new ? reinterpret_cast<float*>(base + w.new_o) : nullptr,
-                      has_new ? reinterpret_cast<float*>(base + w.new_lse) : nullptr, d->new_mode, d->out, nullptr, d->lse,
-                      static_cast<hipStream_t>(stream), (long)x->cap_floats, (long)x->cap_floats, x, 2);
+    FinK f = finish_args(d, nullptr, nullptr, x->world);
+    f.part_o_stride = f.part_lse_stride = (long)x->cap_floats;
+    use_exchange(f, x, 2);
+    merge_to_out(f, d, p.ws);
+    return run_finish(f, d->dtype, static_cast<hipStream_t>(stream));
 }
 
 int ls_lse_merge(const float* parts_o, const float* parts_lse, int n_parts, int b, int sq, int H, int dtype, void* out,
                  float* o32, float* lse, void* stream) {
     if (!parts_o || !parts_lse || n_parts < 1 || b < 1 || sq < 1 || H < 1) LS_FAIL(LS_ERR_INVALID_ARG, "bad merge args");
     ls_attn_desc d = {};
-    d.b = b; d.sq = sq; d.H = H; d.dtype = dtype;
+    d.b = b; d.sq = sq; d.H = H;
     d.out_stride_h = D; d.out_stride_s = (int64_t)H * D; d.out_stride_b = (int64_t)sq * H * D;
-    return run_finish(&d, parts_o, parts_lse, n_parts, nullptr, nullptr, LS_NEW_NONE, out, o32, lse,
-                      static_cast<hipStream_t>(stream));
+    FinK f = finish_args(&d, parts_o, parts_lse, n_parts);
+    f.out = out;
+    f.o32 = o32;
+    f.lse_out = lse;
+    return run_finish(f, dtype, static_cast<hipStream_t>(stream));
 }
 
 int ls_pack_tree_mask(const int64_t* tree_mask, int b, int M, int N, uint32_t* bits, int words, void* stream) {
