@@ -1,0 +1,94 @@
+"""HIP-graph replay of a decode loop's device function: the mechanics ``vanilla_step`` and ``tree_round`` share.
+
+A loop (``llama_glide.py``) keeps its policy -- when a call is eligible, what its keys are, when a key is warmed, captured and
+replayed -- and leaves to ``GraphReplayer`` the capture stream, the memory pool, the tier a capture is sized for, the entries
+per key, the counters and what happens when any of it fails."""
+from __future__ import annotations
+
+import warnings
+from contextlib import contextmanager
+
+import torch
+
+
+class GraphReplayer:
+    """Entries per key: absent, ``"warm"`` (the device function has run once on the capture stream: the operator layer's
+    workspaces are per stream, and lazy one-time work -- weight packing, kernel attributes -- must not fall into a capture)
+    or ``(graph, result, workspace keep-alive)``.
+
+    ``model`` provides ``_tier_bound`` / ``_set_hints`` / ``ops``, looked up at every call; ``hints(bound)`` is the pair of
+    KV-length bounds of a launch sized for ``bound`` emitted tokens of ``total``; ``what`` names the device function in the
+    warning; ``share_pool``: the captures of all keys allocate from one memory pool."""
+
+    def __init__(self, model, hints, total: int, what: str, bound: int = 0, tiers: int = 0, share_pool: bool = False):
+        self.model, self.hints, self.total, self.what, self.share_pool = model, hints, total, what, share_pool
+        self.bound, self.tiers, self.captures = bound, tiers, 0
+        self.entries, self.stream, self.pool = {}, None, None
+        self.disabled = False            # after a failure: the loop runs eagerly from then on
+        self.issued = False              # inside / behind a guard: this call's device work is already on the capture stream
+        self.result = None               # ... and this is what it returned
+
+    def roll_over(self, reached: int):
+        """The generation has got to ``reached`` emitted tokens: past the tier the entries are sized for, drop them and
+        size the next tier's."""
+        if reached > self.bound:
+            self.bound = self.model._tier_bound(reached, self.total)
+            self.entries = {}
+            self.tiers += 1
+
+    def captured(self, key) -> bool:
+        return isinstance(self.entries.get(key), tuple)
+
+    def _set_hints(self):
+        # grid bounds of the current tier, so that a capture stays valid until the generation leaves it
+        self.model._set_hints(*self.hints(self.bound))
+
+    def warm(self, key, device_fn):
+        """Run ``device_fn`` eagerly ON the capture stream, sized like the capture that follows; returns its result."""
+        cur = torch.cuda.current_stream()
+        if self.stream is None:
+            self.stream = torch.cuda.Stream()
+        self._set_hints()
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self.result = device_fn()
+        self.issued = True
+        cur.wait_stream(self.stream)
+        self.entries[key] = "warm"
+        return self.result
+
+    def capture(self, key, device_fn):
+        self._set_hints()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=self.stream, pool=self.pool):
+            result = device_fn()
+        if self.share_pool and self.pool is None:
+            self.pool = graph.pool()
+        # the graph holds raw pointers into the per-stream workspaces of the operator layer
+        ops = self.model.ops
+        keep = ops.workspace_tensors() if hasattr(ops, "workspace_tensors") else None
+        self.entries[key] = (graph, result, keep)
+        self.captures += 1
+
+    def replay(self, key):
+        graph, result, _ = self.entries[key]
+        graph.replay()
+        return result
+
+    @contextmanager
+    def guard(self):
+        """Capture is an optimisation: an environment that cannot do it runs eagerly.  Any exception of the above inside this
+        block (but one raised while a capture is open) becomes one warning and ``disabled``; the block is left, and
+        ``issued`` tells the caller whether the call's device work has run all the same (then ``result`` is its result, and
+        the main stream has been made to wait for it) or is still to be done eagerly."""
+        self.issued, self.result = False, None
+        try:
+            yield
+        except Exception as e:
+            if torch.cuda.is_current_stream_capturing():
+                raise
+            warnings.warn(f"HIP-graph capture of the {self.what} failed ({type(e).__name__}: {e}); running eagerly")
+            self.disabled = True
+            self.entries = {}
+            if self.issued:
+                torch.cuda.current_stream().wait_stream(self.stream)

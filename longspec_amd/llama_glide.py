@@ -14,11 +14,14 @@ Differences from the reference that are deliberate and invisible to callers:
 from __future__ import annotations
 
 import time
+from functools import partial
+from types import SimpleNamespace
 from typing import List, Optional
 
 import torch
 from torch import nn
 
+from .graphs import GraphReplayer
 from .llama import (DecodeLinear, LlamaForCausalLM, LlamaMLP, LlamaRMSNorm, chunked_causal_prefill,
                     project_qkv, _default_ops)
 
@@ -179,6 +182,14 @@ class LlamaGlideDecoderLayer(nn.Module):
         return self.mlp(hidden_states, residual=residual)           # `hidden_states = residual + mlp(...)` (:466)
 
 
+class _DecodeState(SimpleNamespace):
+    """State of a decode loop.  ``use_graphs`` is the caller's switch, honoured at every call; what the loop's
+    ``GraphReplayer`` (``replayer``) has done is read off it."""
+    graphs = property(lambda self: False if self.replayer.disabled else self.replayer.entries)   # `is not False`: replay still on
+    graph_tiers = property(lambda self: self.replayer.tiers)
+    graph_captures = property(lambda self: self.replayer.captures)
+
+
 def _sync(t: torch.Tensor):
     if t.is_cuda:
         torch.cuda.synchronize(t.device)
@@ -327,12 +338,12 @@ class LlamaGlide(LlamaForCausalLM):
     def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int):
         """State of the vanilla loop (``llama_glide.py:566-583``): ``output_ids`` [bsz, max_gen] with the first
         token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32."""
-        from types import SimpleNamespace
         dev = output_ids.device
-        vs = SimpleNamespace(output_ids=output_ids, cache_lens=cache_lens, input_len=input_len, P=prompt_bound, step=0,
-                             rows=torch.arange(output_ids.size(0), device=dev), graph=None, graph_stream=None,
-                             graph_bound=0, graph_captures=0)
+        vs = _DecodeState(output_ids=output_ids, cache_lens=cache_lens, input_len=input_len, P=prompt_bound, step=0,
+                          rows=torch.arange(output_ids.size(0), device=dev))
         vs.use_graphs = bool(dev.type == "cuda" and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
+        P = prompt_bound                                   # (the replayer holds no reference to the state that holds it)
+        vs.replayer = GraphReplayer(self, lambda bound: (P + bound, P + bound), output_ids.size(1), "vanilla step")
         return vs
 
     def _vanilla_device(self, vs):
@@ -347,44 +358,21 @@ class LlamaGlide(LlamaForCausalLM):
     def vanilla_step(self, vs):
         """Decode one token.  On a GPU the step is captured into a HIP graph after GRAPH_AFTER eager steps and replayed."""
         vs.step += 1
-        produced = False                                              # this call's token is already in output_ids (ADVICE r5)
-        if vs.use_graphs:
-            try:
-                if vs.graph is not None and vs.step + 1 > vs.graph_bound:     # (step s reads s rows beyond the prompt's)
-                    vs.graph = None                                           # outgrown: capture the next tier's step
-                if vs.graph is None and vs.step > self.GRAPH_AFTER:
-                    vs.graph_bound = self._tier_bound(vs.step + 1, vs.output_ids.size(1))
-                    self._set_hints(vs.P + vs.graph_bound, vs.P + vs.graph_bound)
-                    cur = torch.cuda.current_stream()
-                    if vs.graph_stream is None:
-                        vs.graph_stream = torch.cuda.Stream()
-                    vs.graph_stream.wait_stream(cur)
-                    with torch.cuda.stream(vs.graph_stream):          # warm the capture stream's workspaces
-                        self._vanilla_device(vs)
-                    produced = True
-                    cur.wait_stream(vs.graph_stream)
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, stream=vs.graph_stream):
-                        self._vanilla_device(vs)
-                    vs.graph = (graph, self.ops.workspace_tensors() if hasattr(self.ops, "workspace_tensors") else None)
-                    vs.graph_captures += 1
-                    return                                            # the warm-up step was this call's token
-                if vs.graph is not None:
-                    vs.graph[0].replay()
-                    return
-            except Exception as e:
-                if torch.cuda.is_current_stream_capturing():
-                    raise
-                import warnings
-                warnings.warn(f"HIP-graph capture of the vanilla step failed ({type(e).__name__}: {e}); running eagerly")
-                vs.use_graphs = False
-                vs.graph = None
-                if produced:                                          # the warm-up step already produced this call's token
-                    if vs.graph_stream is not None:
-                        torch.cuda.current_stream().wait_stream(vs.graph_stream)
-                    return
-                # anything else (a failure in front of the warm-up step -- _set_hints, wait_stream -- or in a later
-                # replay()) has not decoded this call's token: fall through to the eager step
+        if vs.use_graphs and vs.step > self.GRAPH_AFTER:
+            rp, step = vs.replayer, partial(self._vanilla_device, vs)
+            with rp.guard():
+                rp.roll_over(vs.step + 1)                             # (step s reads s rows beyond the prompt's)
+                if rp.captured(None):
+                    rp.replay(None)
+                else:
+                    rp.warm(None, step)                               # the warm-up step is this call's token
+                    rp.capture(None, step)
+                return
+            vs.use_graphs = False
+            if rp.issued:                                             # the warm-up step already produced this call's token
+                return
+            # anything else (a failure in front of the warm-up step -- tier sizing, wait_stream -- or in a later
+            # replay()) has not decoded this call's token: fall through to the eager step
         self._set_hints(vs.P + vs.step, vs.P + vs.step)
         self._vanilla_device(vs)
 
@@ -448,7 +436,6 @@ class LlamaGlide(LlamaForCausalLM):
         = the target's first generated token, ``cache_lens`` [bsz] int32 = valid rows of every cache (the draft's included),
         ``input_len`` [bsz] = prompt length, ``prompt_bound`` = host-side bound of it.  Also the entry point of benchmarks
         that time ``chain_round`` on synthetic KV (bench.py --method seq)."""
-        from types import SimpleNamespace
         bsz = first_token.size(0)
         dev = first_token.device
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
@@ -632,7 +619,6 @@ class LlamaGlide(LlamaForCausalLM):
         ``first_token`` [bsz] = the target's first generated token, ``cache_lens`` [bsz] int32 = valid
         rows of every KV cache, ``prompt_bound`` = host-side bound of it.  Also the entry point of
         synthetic-KV benchmarks, which fill the caches themselves instead of prefilling."""
-        from types import SimpleNamespace
         dev = first_token.device
         bsz = first_token.shape[0]
         cand = [4, 16, 16, 16, 16] if tree_shape is None else list(tree_shape)
@@ -642,7 +628,7 @@ class LlamaGlide(LlamaForCausalLM):
         Fn = acc_n[-1]                       # tree nodes incl. the root
         gamma = len(cand)
         R = Fn - 1 + gamma + 1               # verification rows: [a accepted | F-1 tree | pads]
-        st = SimpleNamespace(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz)
+        st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz)
         st.output_ids = torch.full((bsz, max_gen_len), self._tree_output_fill(eos_id), dtype=torch.int64, device=dev)  # :937 (G8)
         st.spec_mask = torch.zeros((bsz, max_gen_len), dtype=torch.int64, device=dev)
         st.output_ids[:, 0] = first_token
@@ -663,9 +649,12 @@ class LlamaGlide(LlamaForCausalLM):
         # (kernel launches only: dist.PeerExchange) -- callers that bracket kernels with events switch it off per round
         sh = self.model.layers[-1].self_attn.shard
         st.use_graphs = bool(dev.type == "cuda" and (sh is None or sh.graph_safe) and self.GRAPH_ROUNDS)
-        st.graphs, st.graph_stream, st.graph_pool, st.graphs_forced = {}, None, None, False
-        st.graph_bound = self._tier_bound(1, max_gen_len)      # emitted-token bound the captured rounds are sized for
-        st.graph_tiers, st.graph_captures = 1, 0               # diagnostics (tools/e2e_fullsize.py, the soak test)
+        st.graphs_forced = False                               # prepare_tree_graphs: replay from the first round on
+        # the captured rounds are sized for the tier of the first token; st.graph_tiers / st.graph_captures are diagnostics
+        # (tools/e2e_longgen.py, the soak test)
+        P = prompt_bound                                       # (the replayer holds no reference to the state that holds it)
+        st.replayer = GraphReplayer(self, lambda bound: (P + bound + R, P + bound + Fn), max_gen_len, "decode round",
+                                    bound=self._tier_bound(1, max_gen_len), tiers=1, share_pool=True)
         st.tree_mask = torch.zeros((bsz, Fn, Fn), dtype=torch.int64, device=dev)
         st.tree_mask[:, :, 0] = 1
         st.history_logp_sum = torch.zeros((bsz, Fn), dtype=torch.float32, device=dev)
@@ -694,7 +683,7 @@ class LlamaGlide(LlamaForCausalLM):
         kernels the host cannot issue fast enough) become one."""
         a = st.a
         state = None
-        if st.use_graphs and (st.graphs_forced or st.num >= self.GRAPH_AFTER * st.bsz):
+        if st.use_graphs and not st.replayer.disabled and (st.graphs_forced or st.num >= self.GRAPH_AFTER * st.bsz):
             state = self._graph_round(st, a)
         if state is None:
             # host bounds: no cache holds more than P + emitted (+ this round's speculative rows) valid rows
@@ -720,92 +709,42 @@ class LlamaGlide(LlamaForCausalLM):
             return total
         return min(total, (emitted // tier + 1) * tier)
 
-    def _graph_hints(self, st):
-        # grid bounds of the current tier, so that a captured round stays valid until the generation leaves it
-        bound = getattr(st, "graph_bound", None) or st.output_ids.size(1)
-        self._set_hints(st.P + bound + st.R, st.P + bound + st.Fn)
-
-    def _graph_warm(self, st, a: int):
-        """Run the round eagerly ON the capture stream (the operator layer's workspaces are per stream; lazy
-        one-time work -- weight packing, kernel attributes -- must not fall into a capture)."""
-        cur = torch.cuda.current_stream()
-        if st.graph_stream is None:
-            st.graph_stream = torch.cuda.Stream()
-        self._graph_hints(st)
-        st.graph_stream.wait_stream(cur)
-        with torch.cuda.stream(st.graph_stream):
-            state = self._round_device(st, a)
-        cur.wait_stream(st.graph_stream)
-        st.graphs[a] = "warm"
-        return state
-
-    def _graph_capture(self, st, a: int):
-        self._graph_hints(st)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=st.graph_stream, pool=st.graph_pool):
-            state = self._round_device(st, a)
-        if st.graph_pool is None:
-            st.graph_pool = graph.pool()
-        # the graph holds raw pointers into the per-stream workspaces of the operator layer
-        keep = self.ops.workspace_tensors() if hasattr(self.ops, "workspace_tensors") else None
-        st.graphs[a] = (graph, state, keep)
-        st.graph_captures += 1
-        return st.graphs[a]
-
     def _graph_round(self, st, a: int):
         """Replay the HIP graph of a round that starts from ``a`` accepted tokens; the first round with a new ``a``
-        runs eagerly (warm-up), the second one is captured.  Returns the round's state tensor, or None when the
-        round has to run eagerly."""
-        if st.graphs is False:
-            return None
-        if st.emitted > st.graph_bound:          # the generation has outgrown the tier its graphs were sized for
-            st.graph_bound = self._tier_bound(st.emitted, st.output_ids.size(1))
-            st.graphs = {}
-            st.graph_tiers += 1
-        try:
-            g = st.graphs.get(a)
-            if g is None:
-                return self._graph_warm(st, a)
-            if g == "warm":
-                g = self._graph_capture(st, a)
-            g[0].replay()
-            return g[1]
-        except Exception as e:          # capture is an optimisation: an environment that cannot do it runs eagerly
-            if torch.cuda.is_current_stream_capturing():
-                raise
-            import warnings
-            warnings.warn(f"HIP-graph capture of the decode round failed ({type(e).__name__}: {e}); running eagerly")
-            st.graphs = False
-            return None
+        runs eagerly on the capture stream (warm-up), the second one is captured.  Returns the round's state tensor, or
+        None when the round has still to run, eagerly."""
+        rp, device_round = st.replayer, partial(self._round_device, st, a)
+        with rp.guard():
+            rp.roll_over(st.emitted)
+            if a not in rp.entries:
+                return rp.warm(a, device_round)
+            if not rp.captured(a):
+                rp.capture(a, device_round)
+            return rp.replay(a)
+        return rp.result if rp.issued else None       # a warm-up round that was issued IS the round: never run it twice
 
     def prepare_tree_graphs(self, st):
         """Capture the round graphs of every accepted-token count now instead of on first use (benchmarks: keeps the
         captures out of the timed region).  The warm-up rounds run on a snapshot of the decode state: they only
         scribble on cache rows beyond the valid lengths."""
-        if not st.use_graphs or st.graphs is False:
+        rp = st.replayer
+        if not st.use_graphs or rp.disabled:
             return
         st.graphs_forced = True
-        if st.emitted > st.graph_bound:
-            st.graph_bound = self._tier_bound(st.emitted, st.output_ids.size(1))
-            st.graphs = {}
         names = ("cache_lens", "target_cache_lens_for_draft", "draft_cache_lens", "tree_mask", "all_spec", "history_logp_sum",
                  "acc_pad", "output_ids", "emitted_dev")
-        try:
+        with rp.guard():
+            rp.roll_over(st.emitted)
             for a in range(1, st.gamma + 2):
-                if isinstance(st.graphs.get(a), tuple):
+                if rp.captured(a):
                     continue
-                if st.graphs.get(a) is None:
+                device_round = partial(self._round_device, st, a)
+                if a not in rp.entries:
                     snap = {n: getattr(st, n).clone() for n in names}
-                    self._graph_warm(st, a)
+                    rp.warm(a, device_round)
                     for n in names:
                         getattr(st, n).copy_(snap[n])
-                self._graph_capture(st, a)
-        except Exception as e:
-            if torch.cuda.is_current_stream_capturing():
-                raise
-            import warnings
-            warnings.warn(f"HIP-graph capture of the decode round failed ({type(e).__name__}: {e}); running eagerly")
-            st.graphs = False
+                rp.capture(a, device_round)
 
     def _round_device(self, st, a: int):
         """The device work of one round (no host read inside): returns state [bsz, 2] = (acc_num, eos hit).
