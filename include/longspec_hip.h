@@ -282,6 +282,15 @@ size_t ls_topk_workspace_bytes(int rows, int vocab, int k);
 int ls_logprob_topk(const void* logits, int rows, int vocab, int64_t ld, int dtype, const float* history, int k,
                     float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ls_logprob_topk that also keeps the rows' log-probs, the draft's `spec_logits[:, lo:mid] = current_logp` of the
+ * temperature > 0 rounds (longspec/test/llama_glide.py:1025,1074): logp[row * logp_ld + j] = (x[j] - m) - ln sum exp(x - m)
+ * in fp32 for every input row, m and the sum being the ones the top-k values are computed from -- a second pass over the
+ * 16-bit row between the two stages.  logp: 16-byte aligned, logp_ld >= vocab floats and a multiple of 4 (a row slice of
+ * spec_logits [1, Fn, V]).  out_vals / out_idx are bit-identical to ls_logprob_topk on the same input. */
+int ls_logprob_topk_store(const void* logits, int rows, int vocab, int64_t ld, int dtype, const float* history, int k,
+                          float* out_vals, int64_t* out_idx, float* logp, int64_t logp_ld, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* `lm_head(h).argmax(-1)` (llama_glide.py:578,1091): out_idx [rows] int64, first maximum of each row. */
 int ls_argmax_rows(const void* logits, int rows, int vocab, int64_t ld, int dtype, int64_t* out_idx,
                    void* workspace, size_t workspace_bytes, void* stream);
@@ -366,6 +375,21 @@ int ls_tree_commit(const int64_t* acc_ids, const int64_t* acc_num, int b, int ma
                    int64_t out_stride, int out_cap, int emitted, int32_t* emitted_dev, int has_eos, int64_t eos,
                    int64_t* state, int64_t* tree_mask, int64_t* all_spec, float* logp_sum, int F,
                    int32_t* target_lens, int target_add, int32_t* draft_kv_lens, void* stream);
+
+/* End of a round at temperature > 0 (llama_glide.py:1094-1121), what follows verify_stochastic, in one launch:
+ *   output_ids[z, c + j] = acc_ids[z, j] for ALL j < max_acc (the zero padding too), c = cache_lens[z] - input_len[z]
+ *     (cache_lens was advanced by `temp_input_len - 1` only, :1094: the next round overwrites part of this one);
+ *   draft_kv_lens [b] int32 += acc_num (:1110); the tree state reset of ls_tree_commit (:1113-1116);
+ *   acc_pad [b,pad_width] int64 = acc_ids, zero padded (the next round's draft step 0 reads it; may be acc_ids itself);
+ *   state [b,4] int64 = (acc_num, any(output_ids[z, :out_cap] == eos) (:1120), words_used[z] as ls_tree_verify_stochastic
+ *     left it (-1: the pre-drawn words ran out), cache_lens + acc_num - input_len + budget_add > out_cap (:1118, budget_add =
+ *     gamma + 2)) -- the round's single host read.
+ * cache_lens itself is not changed and the accepted KV rows are not compacted, as in the reference's T > 0 branch. */
+int ls_tree_commit_stochastic(const int64_t* acc_ids, const int64_t* acc_num, const int32_t* words_used, int b, int max_acc,
+                              int64_t* output_ids, int64_t out_stride, int out_cap, const int32_t* cache_lens,
+                              const int32_t* input_len, int budget_add, int has_eos, int64_t eos, int64_t* state,
+                              int64_t* tree_mask, int64_t* all_spec, float* logp_sum, int F, int32_t* draft_kv_lens,
+                              int64_t* acc_pad, int pad_width, void* stream);
 
 /* End of a chain-speculation round (spec_generate, llama_glide.py:738-770), gamma draft tokens:
  *   verification = cumprod(llm[:, :-1] == spec[:, 1:]); correct_len = sum + 1; llm[:, 1:] *= verification;

@@ -82,6 +82,7 @@ SYMBOLS = {
     "ls_linear_w8_fwd": (C.c_int, [C.POINTER(LinearDesc), C.POINTER(_P), _P, C.c_size_t, _P]),
     "ls_topk_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "ls_logprob_topk": (C.c_int, [_P, _I, _I, _L, _I, _P, _I, _P, _P, _P, C.c_size_t, _P]),
+    "ls_logprob_topk_store": (C.c_int, [_P, _I, _I, _L, _I, _P, _I, _P, _P, _P, _L, _P, C.c_size_t, _P]),
     "ls_argmax_rows": (C.c_int, [_P, _I, _I, _L, _I, _P, _P, C.c_size_t, _P]),
     "ls_topk_chunk": (C.c_int, []),
     "ls_topk_stage1": (C.c_int, [_P, _I, _I, _L, _I, _I, _I, _I, _P, _P]),
@@ -98,6 +99,7 @@ SYMBOLS = {
     "ls_tree_verify_stochastic": (C.c_int, [_P, _P, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, C.c_float, _P, _I, _P, _P, _I, _P, _P,
                                             _P, _P]),
     "ls_tree_commit": (C.c_int, [_P, _P, _I, _I, _P, _L, _I, _I, _P, _I, _L, _P, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "ls_tree_commit_stochastic": (C.c_int, [_P, _P, _P, _I, _I, _P, _L, _I, _P, _P, _I, _I, _L, _P, _P, _P, _P, _I, _P, _P, _I, _P]),
     "ls_embed_rows": (C.c_int, [_P, _L, _I, _I, _P, _I, _P, _P]),
     "ls_pass_head": (C.c_int, [_P, _L, _I, _I, _P, _I, _P, _P, _I, _I, _P, C.c_float, _P, C.c_float, _P, _P, _P, _P, _P]),
     "ls_chain_commit": (C.c_int, [_P, _P, _I, _I, _P, _L, _I, _P, _P, _P, _P, _I, _L, _P, _P, _P]),

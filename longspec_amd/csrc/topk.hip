@@ -270,6 +270,54 @@ __global__ __launch_bounds__(TK_THREADS) void topk_chunk_kernel(const typename E
     }
 }
 
+// A row's max and log-sum-exp from its chunk records (cm / cs: the row's chunk maxima and sums, in LDS), in fixed chunk order:
+// the merge kernel and the log-prob store below run this same code, so both see the same two floats.
+__device__ __forceinline__ void row_max_lse(const float* cm, const float* cs, int nchunks, float& m_out, float& lse_out) {
+    float m = -INFINITY;
+    for (int c = 0; c < nchunks; ++c) m = fmaxf(m, cm[c]);
+    float s = 0.f;
+    for (int c = 0; c < nchunks; ++c) s += cs[c] * expf(cm[c] - m);
+    m_out = m;
+    lse_out = logf(s);
+}
+
+// Second pass of ls_logprob_topk_store (temperature > 0: the draft's log-prob table, llama_glide.py:1025,1074): one workgroup
+// per (chunk, row) re-reads the 16-bit logits the chunk kernel has just read (L2-resident) and writes
+// logp[row][j] = (x[j] - m) - lse in fp32 -- the merge kernel's operation order, so that a top-k value equals the stored
+// log-prob of its column (+ history) bit for bit.  8 logits per 16-byte load, two 16-byte stores.
+template <typename E>
+__global__ __launch_bounds__(TK_THREADS) void logp_store_kernel(const typename E::T* __restrict__ logits, long ldl, int V, int k,
+                                                                int nchunks, const float* __restrict__ ws,
+                                                                float* __restrict__ logp, long ldp) {
+    __shared__ float s_cm[512], s_cs[512];                         // nchunks <= 512 (host-checked)
+    const int tid = threadIdx.x, chunk = blockIdx.x, row = blockIdx.y, R = gridDim.y;
+    for (int c = tid; c < nchunks; c += TK_THREADS) {
+        const float2 ms = *reinterpret_cast<const float2*>(ws_rec(const_cast<float*>(ws), row, c, R, k));
+        s_cm[c] = ms.x;
+        s_cs[c] = ms.y;
+    }
+    __syncthreads();
+    float m, lse;
+    row_max_lse(s_cm, s_cs, nchunks, m, lse);                      // every thread, on LDS broadcasts: no second barrier
+    const typename E::T* src = logits + (long)row * ldl;
+    float* dst = logp + (long)row * ldp;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = chunk * TK_CHUNK + (j * TK_THREADS + tid) * 8;
+        if (c >= V) continue;                                      // V % 8 == 0: all-in or all-out
+        const uint4 v = *reinterpret_cast<const uint4*>(src + c);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const unsigned short h = (unsigned short)(w[e >> 1] >> ((e & 1) * 16));
+            o[e] = (E::to_f32(__builtin_bit_cast(typename E::T, h)) - m) - lse;
+        }
+        *reinterpret_cast<float4*>(dst + c) = make_float4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<float4*>(dst + c + 4) = make_float4(o[4], o[5], o[6], o[7]);
+    }
+}
+
 // mode 0: joint top-k over all rows of log_softmax(row) + history[row]; out_idx = row * V + column (sorted)
 // mode 1: per-row argmax of the logits; out_idx[row] = column
 // MAXOWN = candidates a thread holds in registers: ceil(R * nchunks * k / 256) rounded up to 4, 8, 16 or 20.  Every extraction round
@@ -307,14 +355,8 @@ __global__ __launch_bounds__(TK_THREADS) void topk_merge_kernel(const float* __r
     }
     for (int row = tid; row < R; row += TK_THREADS) s_h[row] = history ? history[row] : 0.f;
     __syncthreads();
-    for (int row = tid; row < R; row += TK_THREADS) {
-        float m = -INFINITY;
-        for (int c = 0; c < nchunks; ++c) m = fmaxf(m, s_cm[row * nchunks + c]);
-        float s = 0.f;
-        for (int c = 0; c < nchunks; ++c) s += s_cs[row * nchunks + c] * expf(s_cm[row * nchunks + c] - m);
-        s_m[row] = m;
-        s_lse[row] = logf(s);
-    }
+    for (int row = tid; row < R; row += TK_THREADS)
+        row_max_lse(s_cm + row * nchunks, s_cs + row * nchunks, nchunks, s_m[row], s_lse[row]);
     __syncthreads();
     // ---- candidates: R * nchunks * k, strided over the threads and held in registers as (ordered key of the
     // value computed in the reference's operation order, flat index).  Each wave extracts its k best with DPP
@@ -434,17 +476,31 @@ static int stage2(const float* records, int rows, int vocab, int k, int nslots, 
     return LS_OK;
 }
 
+// logp (nullable): the rows' log-probs go to logp[row * logp_ld + column] between the two stages
 static int topk_impl(const void* logits, int rows, int vocab, int64_t ld, int dtype, const float* history, int k, int mode,
-                     float* out_vals, int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream, const char* what) {
+                     float* out_vals, int64_t* out_idx, float* logp, int64_t logp_ld, void* workspace, size_t workspace_bytes,
+                     void* stream, const char* what) {
     int rc = topk_check(logits, rows, vocab, ld, dtype, k, what);
     if (rc) return rc;
     if (!workspace) LS_FAIL(LS_ERR_INVALID_ARG, "%s: null pointer", what);
     const int nchunks = (vocab + TK_CHUNK - 1) / TK_CHUNK;
     if (workspace_bytes < ls_topk_workspace_bytes(rows, vocab, k)) LS_FAIL(LS_ERR_WORKSPACE, "%s: workspace too small", what);
+    if (logp && (logp_ld < vocab || logp_ld % 4 != 0 || reinterpret_cast<uintptr_t>(logp) % 16 != 0 || nchunks > 512))
+        LS_FAIL(LS_ERR_UNSUPPORTED, "%s: logp must be 16-byte aligned with a row stride >= vocab that is a multiple of 4 floats "
+                "(stride %ld, %d chunks)", what, (long)logp_ld, nchunks);
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* ws = static_cast<float*>(workspace);
     rc = stage1(logits, rows, vocab, ld, dtype, k, 0, nchunks, ws, s);
     if (rc) return rc;
+    if (logp) {
+        if (dtype == LS_F16)
+            hipLaunchKernelGGL(logp_store_kernel<ElemF16>, dim3(nchunks, rows), dim3(TK_THREADS), 0, s,
+                               static_cast<const _Float16*>(logits), (long)ld, vocab, k, nchunks, ws, logp, (long)logp_ld);
+        else
+            hipLaunchKernelGGL(logp_store_kernel<ElemBF16>, dim3(nchunks, rows), dim3(TK_THREADS), 0, s,
+                               static_cast<const __bf16*>(logits), (long)ld, vocab, k, nchunks, ws, logp, (long)logp_ld);
+        LS_CHECK_LAUNCH("logp_store_kernel");
+    }
     return stage2(ws, rows, vocab, k, nchunks, history, mode, out_vals, out_idx, s, what);
 }
 
@@ -474,14 +530,22 @@ int ls_topk_stage2(const float* records, int rows, int vocab, int k, int nslots,
 
 int ls_logprob_topk(const void* logits, int rows, int vocab, int64_t ld, int dtype, const float* history, int k, float* out_vals,
                     int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
-    return topk_impl(logits, rows, vocab, ld, dtype, history, k, 0, out_vals, out_idx, workspace, workspace_bytes, stream,
-                     "ls_logprob_topk");
+    return topk_impl(logits, rows, vocab, ld, dtype, history, k, 0, out_vals, out_idx, nullptr, 0, workspace, workspace_bytes,
+                     stream, "ls_logprob_topk");
+}
+
+int ls_logprob_topk_store(const void* logits, int rows, int vocab, int64_t ld, int dtype, const float* history, int k,
+                          float* out_vals, int64_t* out_idx, float* logp, int64_t logp_ld, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    if (!logp) LS_FAIL(LS_ERR_INVALID_ARG, "ls_logprob_topk_store: null logp");
+    return topk_impl(logits, rows, vocab, ld, dtype, history, k, 0, out_vals, out_idx, logp, logp_ld, workspace, workspace_bytes,
+                     stream, "ls_logprob_topk_store");
 }
 
 int ls_argmax_rows(const void* logits, int rows, int vocab, int64_t ld, int dtype, int64_t* out_idx, void* workspace,
                    size_t workspace_bytes, void* stream) {
-    return topk_impl(logits, rows, vocab, ld, dtype, nullptr, 1, 1, nullptr, out_idx, workspace, workspace_bytes, stream,
-                     "ls_argmax_rows");
+    return topk_impl(logits, rows, vocab, ld, dtype, nullptr, 1, 1, nullptr, out_idx, nullptr, 0, workspace, workspace_bytes,
+                     stream, "ls_argmax_rows");
 }
 
 }  // extern "C"

@@ -254,6 +254,51 @@ __global__ __launch_bounds__(TT) void tree_commit_kernel(const int64_t* __restri
     }
 }
 
+// ---- end of a round at temperature > 0 (llama_glide.py:1094-1121) --------------------------------------------------
+// What follows verify_stochastic in the reference's T > 0 branch, in its order and with its quirks: the WHOLE zero-padded
+// acc_ids row (max_acc = gamma + 2 wide) goes to output_ids at column cache_lens - input_len (cache_lens was advanced by
+// a - 1 only, :1094, so the next round overwrites part of this one), draft_kv_lens += acc_num (:1110), the tree state reset
+// (:1113-1116), acc_pad = acc_ids for the next round's draft step 0; the accepted KV rows are not compacted.
+// state[z] = (acc_num, whole-buffer EOS hit (:1120), words_used, cache_lens + acc_num - input_len + budget_add > out_cap
+// (:1118)) is the round's one host read.
+__global__ __launch_bounds__(TT) void tree_commit_stochastic_kernel(
+    const int64_t* __restrict__ acc_ids, const int64_t* __restrict__ acc_num, const int32_t* __restrict__ words_used, int max_acc,
+    int64_t* __restrict__ output_ids, long out_stride, int out_cap, const int32_t* __restrict__ cache_lens,
+    const int32_t* __restrict__ input_len, int budget_add, int has_eos, int64_t eos, int64_t* __restrict__ state,
+    int64_t* __restrict__ tree_mask, int64_t* __restrict__ all_spec, float* __restrict__ logp_sum, int F, int32_t* draft_kv_lens,
+    int64_t* acc_pad, int pad_width) {
+    __shared__ int s_hit;
+    const int z = blockIdx.x, tid = threadIdx.x;
+    const int n = (int)acc_num[z];
+    const long col = (long)cache_lens[z] - (long)input_len[z];
+    int64_t* out = output_ids + (long)z * out_stride;
+    if (tid == 0) s_hit = 0;
+    const int64_t mine = tid < max_acc ? acc_ids[(long)z * max_acc + tid] : 0;
+    const int64_t next_root = acc_ids[(long)z * max_acc + min(max(n, 1), max_acc) - 1];
+    if (tid < max_acc && col + tid >= 0 && col + tid < out_cap) out[col + tid] = mine;
+    __syncthreads();                                   // (acc_pad may be acc_ids itself: every read of it is above)
+    if (tid < pad_width) acc_pad[(long)z * pad_width + tid] = mine;
+    if (has_eos) {
+        int hit = 0;
+        for (int i = tid; i < out_cap; i += TT) hit |= out[i] == eos;
+        if (hit) atomicOr(&s_hit, 1);
+    }
+    int64_t* mask = tree_mask + (long)z * F * F;
+    for (int i = tid; i < F * F; i += TT) mask[i] = (i % F) == 0 ? 1 : 0;
+    for (int i = tid; i < F; i += TT) {
+        all_spec[(long)z * F + i] = i == 0 ? next_root : 0;
+        logp_sum[(long)z * F + i] = 0.f;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        state[4 * z] = n;
+        state[4 * z + 1] = s_hit;
+        state[4 * z + 2] = words_used[z];
+        state[4 * z + 3] = col + n + budget_add > out_cap ? 1 : 0;
+        draft_kv_lens[z] += n;
+    }
+}
+
 // ---- end of a chain-speculation round (llama_glide.py:738-770) -------------------------------------------------------
 // verification = cumprod(llm[:, :-1] == spec[:, 1:]); correct_len = sum + 1; the verified ids and the bonus token go to
 // output_ids; cache_lens += correct_len; the next round's start tokens; state = (correct_len, eos hit).  One wave per row.
@@ -557,6 +602,24 @@ int ls_tree_commit(const int64_t* acc_ids, const int64_t* acc_num, int b, int ma
                        output_ids, (long)out_stride, out_cap, emitted, emitted_dev, has_eos, eos, state, tree_mask, all_spec,
                        logp_sum, F, target_lens, target_add, draft_kv_lens);
     LS_CHECK_LAUNCH("tree_commit_kernel");
+    return LS_OK;
+}
+
+int ls_tree_commit_stochastic(const int64_t* acc_ids, const int64_t* acc_num, const int32_t* words_used, int b, int max_acc,
+                              int64_t* output_ids, int64_t out_stride, int out_cap, const int32_t* cache_lens,
+                              const int32_t* input_len, int budget_add, int has_eos, int64_t eos, int64_t* state,
+                              int64_t* tree_mask, int64_t* all_spec, float* logp_sum, int F, int32_t* draft_kv_lens,
+                              int64_t* acc_pad, int pad_width, void* stream) {
+    if (!acc_ids || !acc_num || !words_used || !output_ids || !cache_lens || !input_len || !state || !tree_mask || !all_spec ||
+        !logp_sum || !draft_kv_lens || !acc_pad)
+        LS_FAIL(LS_ERR_INVALID_ARG, "tree_commit_stochastic: null pointer");
+    if (b < 1 || F < 1 || F > MAXF || max_acc < 1 || max_acc > TT || pad_width < max_acc || pad_width > TT || out_cap < 1 ||
+        out_stride < out_cap || budget_add < 0)
+        LS_FAIL(LS_ERR_INVALID_ARG, "tree_commit_stochastic: F=%d max_acc=%d pad_width=%d out_cap=%d", F, max_acc, pad_width, out_cap);
+    hipLaunchKernelGGL(tree_commit_stochastic_kernel, dim3(b), dim3(TT), 0, static_cast<hipStream_t>(stream), acc_ids, acc_num,
+                       words_used, max_acc, output_ids, (long)out_stride, out_cap, cache_lens, input_len, budget_add, has_eos, eos,
+                       state, tree_mask, all_spec, logp_sum, F, draft_kv_lens, acc_pad, pad_width);
+    LS_CHECK_LAUNCH("tree_commit_stochastic_kernel");
     return LS_OK;
 }
 

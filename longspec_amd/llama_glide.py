@@ -233,6 +233,7 @@ class LlamaGlide(LlamaForCausalLM):
     GRAPH_AFTER = 256        # ... once a generation has run this many rounds: a capture costs ~10 ms and a replay saves
                              # <= 0.1 ms on a fast host (more on a slow or busy one), so only long generations
                              # (LongSpec's long-CoT case) pay it back; benchmarks capture up front (prepare_tree_graphs)
+    GRAPH_STOCHASTIC = True  # ... the rounds at temperature > 0 too (tree_round_stochastic); False: launch by launch
     GRAPH_TIER = 4096        # a captured round / step is sized (host-side bounds of the KV lengths -> launch grids, split
                              # counts, kernel choice) for the tokens emitted so far rounded up to the next multiple of this;
                              # a generation that outgrows its tier drops its graphs and captures the next tier's (a 20 000-token
@@ -663,12 +664,15 @@ class LlamaGlide(LlamaForCausalLM):
         st.temperature = float(temperature)
         if temperature > 0:
             # stochastic verification (:1093-1102): the draft's log-probs of every tree node are kept (`spec_logits`, :964),
-            # up to gamma + 2 tokens come back per round, rounds run launch by launch (a host read inside)
+            # up to gamma + 2 tokens come back per round.  Rounds run launch by launch (host reads inside) until the
+            # generation is GRAPH_AFTER rounds old, then from HIP graphs keyed by (a, d0_rows): batch 1 only
             st.spec_logits = None                      # allocated at the first lm_head call (vocabulary size)
             st.acc_pad = torch.zeros((bsz, gamma + 2), dtype=torch.int64, device=dev)
             st.acc_pad[:, 0] = first_token
             st.acc_ids = st.acc_pad[:, :1]
-            st.use_graphs = False
+            st.use_graphs = bool(st.use_graphs and self.GRAPH_STOCHASTIC and bsz == 1)
+            st.fused_logp = False                      # the graph path: spec_logits is written by ops.logprob_topk
+            st.mt_host = st.mt_words = st.noise = None  # ... and the round's random draws live in persistent buffers
             st.input_len = cache_lens.clone()
             st.d0_rows = 1                             # rows of the next draft step 0 = width of the last acc_ids
         return st
@@ -713,14 +717,18 @@ class LlamaGlide(LlamaForCausalLM):
         """Replay the HIP graph of a round that starts from ``a`` accepted tokens; the first round with a new ``a``
         runs eagerly on the capture stream (warm-up), the second one is captured.  Returns the round's state tensor, or
         None when the round has still to run, eagerly."""
-        rp, device_round = st.replayer, partial(self._round_device, st, a)
+        return self._replay_round(st, a, partial(self._round_device, st, a))
+
+    def _replay_round(self, st, key, device_round):
+        """Warm-up, capture or replay of ``device_round`` under ``key`` (``_graph_round``, ``_graph_round_stochastic``)."""
+        rp = st.replayer
         with rp.guard():
             rp.roll_over(st.emitted)
-            if a not in rp.entries:
-                return rp.warm(a, device_round)
-            if not rp.captured(a):
-                rp.capture(a, device_round)
-            return rp.replay(a)
+            if key not in rp.entries:
+                return rp.warm(key, device_round)
+            if not rp.captured(key):
+                rp.capture(key, device_round)
+            return rp.replay(key)
         return rp.result if rp.issued else None       # a warm-up round that was issued IS the round: never run it twice
 
     def prepare_tree_graphs(self, st):
@@ -729,6 +737,8 @@ class LlamaGlide(LlamaForCausalLM):
         scribble on cache rows beyond the valid lengths."""
         rp = st.replayer
         if not st.use_graphs or rp.disabled:
+            return
+        if st.temperature > 0:      # the stochastic rounds capture on first use only (keys (a, d0_rows), tree_round_stochastic)
             return
         st.graphs_forced = True
         names = ("cache_lens", "target_cache_lens_for_draft", "draft_cache_lens", "tree_mask", "all_spec", "history_logp_sum",
@@ -776,8 +786,12 @@ class LlamaGlide(LlamaForCausalLM):
             if st.temperature > 0:                     # spec_logits[:, 0] = current_logp (:1025, G8: log-probs, not logits)
                 if st.spec_logits is None:
                     st.spec_logits = torch.zeros((bsz, Fn, vocab_size), dtype=torch.float32, device=logits.device)
-                st.spec_logits[:, 0] = logits[:, 0].float().log_softmax(dim=-1)
-            topk_logp, pred_ids = ops.logprob_topk(logits, None, cand[0])
+                if not st.fused_logp:
+                    st.spec_logits[:, 0] = logits[:, 0].float().log_softmax(dim=-1)
+            if st.temperature > 0 and st.fused_logp:   # the graph path: the top-k launches store the row themselves
+                topk_logp, pred_ids = ops.logprob_topk(logits, None, cand[0], logp_out=st.spec_logits[:, 0:1])
+            else:
+                topk_logp, pred_ids = ops.logprob_topk(logits, None, cand[0])
         # the root's children (:1021-1027): tree_mask rows + diagonal, all_spec, log-prob sums, and
         # `draft_cache_lens += a - 1` -- one launch, which also hands back the next pass's positions and packed mask
         position_ids, mask_bits = ops.tree_grow(tree_mask, all_spec, history_logp_sum, topk_logp, pred_ids, vocab_size, 0, 1,
@@ -796,9 +810,13 @@ class LlamaGlide(LlamaForCausalLM):
                                                               history=history_logp_sum[:, lo:mid])
             else:
                 level_logits = self.lm_head(hidden_states)
-                if st.temperature > 0:                 # spec_logits[:, lo:mid] = current_logp (:1074)
-                    st.spec_logits[:, lo:mid] = level_logits.float().log_softmax(dim=-1)
-                topk_logp_sum, topk_indices = ops.logprob_topk(level_logits, history_logp_sum[:, lo:mid], cand[ms])
+                if st.temperature > 0 and st.fused_logp:
+                    topk_logp_sum, topk_indices = ops.logprob_topk(level_logits, history_logp_sum[:, lo:mid], cand[ms],
+                                                                   logp_out=st.spec_logits[:, lo:mid])
+                else:
+                    if st.temperature > 0:             # spec_logits[:, lo:mid] = current_logp (:1074)
+                        st.spec_logits[:, lo:mid] = level_logits.float().log_softmax(dim=-1)
+                    topk_logp_sum, topk_indices = ops.logprob_topk(level_logits, history_logp_sum[:, lo:mid], cand[ms])
             # father = index // vocab, token = index % vocab, mask row = father's row + diagonal (:1056-1075)
             position_ids, mask_bits = ops.tree_grow(tree_mask, all_spec, history_logp_sum, topk_logp_sum, topk_indices,
                                                     vocab_size, lo, mid, base=st.draft_cache_lens, want_next=ms + 1 < gamma)
@@ -844,6 +862,8 @@ class LlamaGlide(LlamaForCausalLM):
             # the reference fails here too: gamma + 2 accepted tokens do not fit its veri_spec buffer (:1081)
             raise RuntimeError(f"stochastic round: {a} accepted tokens + {st.Fn - 1} tree nodes exceed the {st.R}-row "
                                f"verification batch (the reference raises at llama_glide.py:1081 in the same state)")
+        if st.use_graphs and not st.replayer.disabled and st.num >= self.GRAPH_AFTER * st.bsz:
+            return self._graph_round_stochastic(st, a)
         # host bound of the valid rows, per round as in the eager T = 0 path: every round reads acc_num on the host anyway, and
         # the lengths (cache_lens advances by a - 1 per round, the draft's by acc_num) never exceed P + the sum of the accepted
         # counts -- NOT the whole token budget, which sized a 1k-prompt / 20k-budget run for 21k-row launches from round 1
@@ -874,6 +894,72 @@ class LlamaGlide(LlamaForCausalLM):
         if int((st.cache_lens + acc_num.to(torch.int32) - st.input_len).max()) + st.gamma + 2 > st.output_ids.size(1):   # :1118
             return False
         if st.eos is not None and bool(st.output_ids.eq(st.eos).any()):      # :1120
+            return False
+        return True
+
+    def _stochastic_device(self, st, a: int):
+        """The device work of one round at temperature > 0 (no host read inside): the draft passes with the log-prob table
+        stored by the top-k launches, the verification pass, ``cache_lens += a - 1`` (:1094), the acceptance walk on the
+        pre-drawn randomness in ``st.mt_words`` / ``st.noise`` and the commit.  Returns state [1, 4] = (acc_num, eos hit,
+        words_used, budget exhausted)."""
+        ops = self.ops
+        st.fused_logp = True
+        try:
+            llm_logits = self._round_device(st, a)                           # [1, Fn, V]
+        finally:
+            st.fused_logp = False                                            # (the eager rounds keep torch's log_softmax)
+        st.cache_lens += a - 1
+        # a beam tree grown from tree_shape has depth gamma: the reference's `tree_mask.sum(-1).max() + 1` (:1193) is gamma + 2
+        acc_ids, acc_num, used = ops.tree_verify_stochastic(st.all_spec, st.tree_mask, llm_logits, st.spec_logits, st.temperature,
+                                                            st.mt_words, st.noise, st.gamma + 2)
+        return ops.tree_commit_stochastic(acc_ids, acc_num, used, st.output_ids, st.cache_lens, st.input_len, st.gamma, st.eos,
+                                          st.tree_mask, st.all_spec, st.history_logp_sum, st.target_cache_lens_for_draft,
+                                          st.acc_pad)
+
+    def _graph_round_stochastic(self, st, a: int) -> bool:
+        """``tree_round_stochastic`` from a HIP graph per (a, d0_rows): one replay and ONE host read per round.  The random
+        streams are the eager path's, drawn once per round out here -- ``ops.MT_WORDS`` words of Python's ``random`` (rewound
+        after the read to what the walk consumed, as ``ops.verify_stochastic`` does) and one Exponential(1) row -- and copied
+        into the persistent buffers the captured walk reads.  Whatever becomes of the capture (warm-up, replay, or a failure
+        that sends this round and all later ones down the eager road), these draws are the round's only ones."""
+        import random
+        import numpy as np
+        ops, dev, W = self.ops, st.dev, st.gamma + 2
+        V, dtype = self.lm_head.out_features, self.model.embed_tokens.weight.dtype
+        if st.mt_words is None:                        # nothing is allocated inside a capture
+            if st.spec_logits is None:
+                st.spec_logits = torch.zeros((st.bsz, st.Fn, V), dtype=torch.float32, device=dev)
+            st.mt_host = torch.empty((1, ops.MT_WORDS), dtype=torch.int32).pin_memory()
+            st.mt_words = torch.empty((1, ops.MT_WORDS), dtype=torch.int32, device=dev)
+            st.noise = torch.empty((1, V), dtype=dtype, device=dev)
+        rng_state = random.getstate()
+        words = random.getrandbits(32 * ops.MT_WORDS).to_bytes(4 * ops.MT_WORDS, "little")   # = MT_WORDS x getrandbits(32)
+        st.mt_host.numpy()[0, :] = np.frombuffer(words, dtype=np.int32)
+        noise_fn = getattr(ops, "stochastic_noise_fn", None)
+        noise = noise_fn(V, dtype, dev) if noise_fn is not None else torch.empty((V,), dtype=dtype, device=dev).exponential_(1)
+        st.mt_words.copy_(st.mt_host, non_blocking=True)       # (the round's host read below is behind this copy)
+        st.noise.copy_(noise.view(1, V))
+        device_round = partial(self._stochastic_device, st, a)
+        state = self._replay_round(st, (a, st.d0_rows), device_round)
+        if state is None:                              # the capture failed before the round was issued: eagerly, same draws
+            bound = min(st.emitted, st.output_ids.size(1))
+            self._set_hints(st.P + bound + st.R, st.P + bound + st.Fn)
+            state = device_round()
+        n, hit, used, over = state.tolist()[0]                               # the round's ONE host read
+        if used < 0:
+            raise RuntimeError("verify_stochastic: the pre-drawn random words were exhausted")
+        random.setstate(rng_state)
+        if used:
+            random.getrandbits(32 * used)
+        st.acc_ids = st.acc_pad[:, :n]
+        st.a = n
+        st.d0_rows = W
+        st.emitted += n
+        st.count += n - 1
+        st.num += st.bsz
+        if over:                                                             # :1118
+            return False
+        if hit:                                                              # :1120
             return False
         return True
 

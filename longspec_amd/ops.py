@@ -10,6 +10,8 @@ One function per reference seam of the draft-then-verify round:
   tree_collapse          LlamaGlide.tree_verification  llama_glide.py:1128-1175
   lse_merge              N-way form of llama.py:385-387,420 for sequence-sharded prefix KV
   logprob_topk / argmax_rows   beam growth and greedy verification on the lm_head logits  llama_glide.py:1019-1064,1091
+                         (logp_out=: the draft's log-prob table of the temperature > 0 rounds, :1025,1074)
+  tree_commit / tree_commit_stochastic   end of a round at temperature 0 / > 0  llama_glide.py:1093-1121
   linear / linear_multi / mlp_gate_up   the projections of a decode pass (M <= 80 token rows):
                          q/k/v/o_proj llama.py:361-363,390, LlamaMLP (qwen2.py:218-230), lm_head llama_glide.py:1091
                          -- with 16-bit (pack_weight) or 8-bit e4m3 (pack_weight8) packed weights
@@ -221,20 +223,28 @@ def pack_gate_up8(gate_weight, up_weight) -> PackedWeight8:
     return PackedWeight8(out, torch.stack([sg, su]).contiguous(), N, K, pair=True)
 
 
-def logprob_topk(logits: torch.Tensor, history: Optional[torch.Tensor], k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+def logprob_topk(logits: torch.Tensor, history: Optional[torch.Tensor], k: int,
+                 logp_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(logits.float().log_softmax(-1) + history[..., None]).view(bsz, -1).topk(k)`` (llama_glide.py:1019-1020,
     1046-1064) straight from the fp16 lm_head output: logits [bsz, rows, V], history [bsz, rows] fp32 or None ->
-    (values [bsz, k] fp32 descending, flat indices [bsz, k] int64 = row * V + column)."""
-    _dev(logits, history)
+    (values [bsz, k] fp32 descending, flat indices [bsz, k] int64 = row * V + column).
+    ``logp_out`` [bsz, rows, V] fp32 (a row slice of ``spec_logits``, :1025,1074): also receives
+    ``logits.float().log_softmax(-1)``, written by the same launch sequence (``ls_logprob_topk_store``); the returned
+    values and indices do not depend on it."""
+    _dev(logits, history, logp_out)
     if logits.dim() == 2:
         logits = logits.unsqueeze(1)
     if (logits.stride(-1) != 1 or logits.stride(1) % 8 != 0 or (logits.shape[0] > 1 and logits.stride(0) % 8 != 0)
             or logits.data_ptr() % 16 != 0):                           # the kernel loads 16 bytes at a time
         logits = logits.contiguous()
     b, R, V = logits.shape
+    if logp_out is not None and (logp_out.dtype != torch.float32 or tuple(logp_out.shape) != (b, R, V) or logp_out.stride(-1) != 1):
+        raise TypeError("logprob_topk: logp_out must be fp32 [bsz, rows, V] with a contiguous last dimension")
     if k > 64 or R > 128 or R * ((V + 8191) // 8192) * k > 5120 or R * ((V + 8191) // 8192) > 512 or V % 8:
         # beyond the fused kernel's candidate budget (trees wider than BASELINE's 16 per level): library kernels
         lp = logits.float().log_softmax(dim=-1)
+        if logp_out is not None:
+            logp_out.copy_(lp)
         if history is not None:
             lp = lp + history[:, :, None].float()
         return lp.view(b, -1).topk(dim=-1, k=k, largest=True, sorted=True)
@@ -246,9 +256,14 @@ def logprob_topk(logits: torch.Tensor, history: Optional[torch.Tensor], k: int) 
     need = lib.ls_topk_workspace_bytes(R, V, k)
     ws = _ws.get(logits.device, max(need, 1))
     for i in range(b):
-        _C.check(lib.ls_logprob_topk(logits[i].data_ptr(), R, V, logits.stride(1), _dtype(logits),
-                                     history[i].data_ptr() if history is not None else None, k, vals[i].data_ptr(),
-                                     idx[i].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "ls_logprob_topk")
+        hist = history[i].data_ptr() if history is not None else None
+        if logp_out is None:
+            _C.check(lib.ls_logprob_topk(logits[i].data_ptr(), R, V, logits.stride(1), _dtype(logits), hist, k, vals[i].data_ptr(),
+                                         idx[i].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "ls_logprob_topk")
+        else:
+            _C.check(lib.ls_logprob_topk_store(logits[i].data_ptr(), R, V, logits.stride(1), _dtype(logits), hist, k,
+                                               vals[i].data_ptr(), idx[i].data_ptr(), logp_out[i].data_ptr(), logp_out.stride(1),
+                                               ws.data_ptr(), ws.numel(), _stream()), "ls_logprob_topk_store")
     return vals, idx
 
 
@@ -1131,6 +1146,34 @@ def tree_commit(acc_ids, acc_num, output_ids, emitted: int, eos: Optional[int], 
                                 0 if eos is None else int(eos), state.data_ptr(), tree_mask.data_ptr(), all_spec.data_ptr(),
                                 logp_sum.data_ptr(), Fn, _len_i32(target_lens, b, "target_lens"), target_add,
                                 _len_i32(draft_kv_lens, b, "draft_kv_lens"), _stream()), "ls_tree_commit")
+    return state
+
+
+def tree_commit_stochastic(acc_ids, acc_num, words_used, output_ids, cache_lens, input_len, gamma: int, eos: Optional[int],
+                           tree_mask, all_spec, logp_sum, draft_kv_lens, acc_pad) -> torch.Tensor:
+    """End of a round at temperature > 0 (``llama_glide.py:1094-1121``) in one launch (``ls_tree_commit_stochastic``): the whole
+    zero-padded ``acc_ids`` row goes to ``output_ids`` at column ``cache_lens - input_len``, ``draft_kv_lens += acc_num``, the
+    tree state is reset (mask = root column, all_spec[0] = the last accepted id, log-prob sums = 0) and ``acc_pad = acc_ids``.
+    Returns state [b,4] int64 = (acc_num, whole-buffer EOS hit, words_used, ``cache_lens + acc_num - input_len + gamma + 2 >
+    output_ids.size(1)``) -- the round's one host read.  ``cache_lens`` is read, not advanced (:1094 runs before the walk)."""
+    _dev(acc_ids, acc_num, words_used, output_ids, cache_lens, input_len, tree_mask, all_spec, logp_sum, draft_kv_lens, acc_pad)
+    b, Fn = _tree_state(tree_mask, all_spec, logp_sum)
+    for t, name in ((acc_ids, "acc_ids"), (acc_pad, "acc_pad")):
+        if t.dtype != torch.int64 or t.dim() != 2 or t.shape[0] != b or not t.is_contiguous():
+            raise TypeError(f"tree_commit_stochastic: {name} must be a contiguous int64 [b, width] tensor")
+    if output_ids.dtype != torch.int64 or output_ids.stride(1) != 1 or acc_num.dtype != torch.int64 or not acc_num.is_contiguous():
+        raise TypeError("tree_commit_stochastic: output_ids / acc_num must be int64 with contiguous rows")
+    if words_used.dtype != torch.int32 or words_used.numel() != b or not words_used.is_contiguous():
+        raise TypeError("tree_commit_stochastic: words_used must be a contiguous int32 [b] tensor")
+    if acc_pad.shape[1] < acc_ids.shape[1]:
+        raise ValueError("tree_commit_stochastic: acc_pad is narrower than acc_ids")
+    state = torch.empty((b, 4), dtype=torch.int64, device=all_spec.device)
+    _C.check(_C.load().ls_tree_commit_stochastic(
+        acc_ids.data_ptr(), acc_num.data_ptr(), words_used.data_ptr(), b, acc_ids.shape[1], output_ids.data_ptr(),
+        output_ids.stride(0), output_ids.shape[1], _len_i32(cache_lens, b, "cache_lens"), _len_i32(input_len, b, "input_len"),
+        gamma + 2, 0 if eos is None else 1, 0 if eos is None else int(eos), state.data_ptr(), tree_mask.data_ptr(),
+        all_spec.data_ptr(), logp_sum.data_ptr(), Fn, _len_i32(draft_kv_lens, b, "draft_kv_lens"), acc_pad.data_ptr(),
+        acc_pad.shape[1], _stream()), "ls_tree_commit_stochastic")
     return state
 
 
