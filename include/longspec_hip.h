@@ -358,7 +358,9 @@ int ls_tree_collapse(const int64_t* all_spec, const int64_t* all_llm_pred, const
  *   exp_noise [b,V] dtype = torch.empty(V).exponential_(1): multinomial(p, 1) is argmax(p / noise) (ATen's one-sample path).
  * acc_ids [b,max_acc] int64 zero padded (max_acc >= tree depth + 2), acc_num [b] int64; workspace: b*V floats.
  * Kept from the reference on purpose: the acceptance ratio of child NODE s reads both distributions at vocabulary index s
- * (:1222); target probabilities are rounded to dtype after every operation (:1186,1231-1235). */
+ * (:1222); target probabilities are rounded to dtype after every operation (:1186,1231-1235).
+ * LS_ERR_INVALID_ARG, before any launch: V < F (vocabulary index s of a child node would be out of range; the reference
+ * raises an IndexError there), max_acc outside 2..15, n_words < 3, temperature <= 0. */
 int ls_tree_verify_stochastic(const int64_t* all_spec, const int64_t* tree_mask, const void* llm_logits, int64_t logits_stride_b,
                               int64_t logits_stride_r, const float* spec_logp, int64_t logp_stride_b, int64_t logp_stride_r,
                               int b, int F, int Fs, int V, int dtype, float temperature, const uint32_t* mt_words, int n_words,

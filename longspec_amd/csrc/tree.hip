@@ -493,6 +493,7 @@ __global__ __launch_bounds__(TT) void tree_verify_stochastic_kernel(
             }
             __syncthreads();
             if (sh_taken >= 0 || sh_reject < 0) break;
+            const int left = sh_n;            // read before the barriers below: thread 0 rewrites sh_n in the next pass
             // residual distribution of the target at cur: max(p - q, 0), renormalised, every step rounded to E
             float part = 0.f;
             for (int j = tid; j < V; j += TT) {
@@ -505,7 +506,7 @@ __global__ __launch_bounds__(TT) void tree_verify_stochastic_kernel(
             if (tot > 0.f)
                 for (int j = tid; j < V; j += TT) prow[j] = round_to<E>(prow[j] / tot);
             __syncthreads();
-            if (sh_n == 0) break;
+            if (left == 0) break;
         }
         if (sh_taken < 0) break;
         if (tid == 0) {
@@ -660,6 +661,8 @@ int ls_tree_verify_stochastic(const int64_t* all_spec, const int64_t* tree_mask,
     if (b < 1 || F < 1 || F > MAXF || Fs < 1 || V < 1 || max_acc < 2 || max_acc > 15 || n_words < 3 || !(temperature > 0.f))
         LS_FAIL(LS_ERR_INVALID_ARG, "verify_stochastic: b=%d F=%d Fs=%d V=%d max_acc=%d n_words=%d T=%g", b, F, Fs, V, max_acc,
                 n_words, (double)temperature);
+    // the acceptance ratio of child node s reads both distributions at vocabulary index s < F (the reference's quirk)
+    if (V < F) LS_FAIL(LS_ERR_INVALID_ARG, "verify_stochastic: V=%d is smaller than F=%d", V, F);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == LS_F16)
         hipLaunchKernelGGL(tree_verify_stochastic_kernel<ElemF16>, dim3(b), dim3(TT), 0, s, all_spec, tree_mask,

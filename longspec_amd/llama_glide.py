@@ -946,9 +946,9 @@ class LlamaGlide(LlamaForCausalLM):
             self._set_hints(st.P + bound + st.R, st.P + bound + st.Fn)
             state = device_round()
         n, hit, used, over = state.tolist()[0]                               # the round's ONE host read
+        random.setstate(rng_state)
         if used < 0:
             raise RuntimeError("verify_stochastic: the pre-drawn random words were exhausted")
-        random.setstate(rng_state)
         if used:
             random.getrandbits(32 * used)
         st.acc_ids = st.acc_pad[:, :n]

@@ -1116,9 +1116,9 @@ def verify_stochastic(input_ids, tree_mask, p_llm, p_ssm, temperature: float):
         ids, num, used = tree_verify_stochastic(input_ids[z:z + 1], tree_mask[z:z + 1], p_llm[z:z + 1], p_ssm[z:z + 1],
                                                 temperature, mt, noise[None], max(width, 2))
         used = int(used[0])
-        if used < 0:
-            raise RuntimeError("verify_stochastic: the pre-drawn random words were exhausted")
         random.setstate(state)
+        if used < 0:                      # Python's generator stays where it was before the call
+            raise RuntimeError("verify_stochastic: the pre-drawn random words were exhausted")
         for _ in range(used):
             random.getrandbits(32)
         acc_ids[z] = ids[0, :width]
