@@ -247,6 +247,49 @@ size_t ls_linear_w8_workspace_bytes(const ls_linear_desc* d);
 int ls_linear_w8_fwd(const ls_linear_desc* d, const float* const scale[3], void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- the same linear layers with 4-bit (OCP MX FP4) weights --------------------------------------
+ *
+ * W[n, k] = e2m1(q[n, k]) * 2^(e[n, k/32] - 127): 4-bit elements {+-0, 0.5, 1, 1.5, 2, 3, 4, 6} (sign, 2 exponent bits, 1
+ * mantissa bit), two per byte with the lower k in the low nibble, and one e8m0 scale byte per 32 consecutive k of a row.
+ * No counterpart in the reference (longspec/test keeps 16-bit weights); the seams served are ls_linear_fwd's:
+ * llama.py:361-363,390, LlamaMLP.forward (vendored qwen2.py:218-230), llama_glide.py:248-250,268,285-287,305, lm_head at
+ * llama_glide.py:960,1019,1046,1091.
+ * Activations, bias, accumulation (fp32, MFMA f16/bf16) and every rounding point are those of ls_linear_fwd; the nibbles
+ * are converted on their way into the MFMA operand (v_cvt_scalef32_pk_{f16,bf16}_fp4) with the block scale as the
+ * instruction's scale operand, so no scale is applied behind the sums.  This path takes scale bytes in [114, 140]
+ * (2^-13 .. 2^13) only: every non-zero de-quantised value is then a normal fp16 and an exact bf16 number and
+ * ls_linear_w4_fwd is BIT-IDENTICAL to ls_linear_fwd on the de-quantised 16-bit weight for the same descriptor (same
+ * n_splits): the launch plan and the k order of every row are shared.
+ *
+ * Packed layout: ceil(N/64) * (K/64) * 2176 bytes; the chunk of (64-row group g, 64-wide k chunk c) sits at byte offset
+ * (g*(K/64) + c)*2176 and holds, for tile t = 0..3 and lane l = 0..63, the 4 bytes (8 nibbles)
+ * q[64g + 16t + l%16][64c + 8(l/16) .. +8] at 512*t + 8*l and the 4 bytes q[same row][64c + 32 + 8(l/16) .. +8] at
+ * 512*t + 8*l + 4, followed at 2048 + 8*r + 2*t + ks by the scale byte e[64g + 16t + r][2c + ks] (r = 0..15, ks = 0, 1).
+ * Rows >= N are zero.  0.5 + 1/32 bytes are streamed per weight element.
+ */
+size_t ls_linear_w4_packed_bytes(int N, int K);
+
+/* Block quantiser: weight [N, K] dtype (row-major, contiguous, K % 32 == 0) -> q [N, K/2] nibble bytes, e [N, K/32] e8m0.
+ *   amax = max |w| over the 32-k block;  E = ceil(log2(amax / 6)) by exponent arithmetic, clamped to [-13, 13];
+ *   amax == 0 -> E = 0;  e = E + 127;  element = e2m1(w / 2^E), round to nearest, ties to the even mantissa bit, saturating
+ *   at +-6, the sign of w kept (a zero magnitude included).
+ * Bit for bit what longspec_amd/quant.py::quantize_blocks_mxfp4 computes on the host. */
+int ls_linear_w4_quantize(const void* weight, int N, int K, int dtype, uint8_t* q, uint8_t* e, void* stream);
+
+/* (q, e) -> the streamed layout (K % 64 == 0).  q_up / e_up != NULL: a gate/up pair of an MLP with alternating 16-row
+ * tiles (2N rows, N % 16 == 0: the operand of LS_EPI_SILU_MUL, as ls_linear_pack_gate_up).  rope != 0: the q/k layout of
+ * LS_EPI_QKV_ROPE (N = heads x 128, as ls_linear_pack_rope).  A scale byte outside [114, 140] is LS_ERR_UNSUPPORTED (a
+ * checkpoint quantised elsewhere with a wider exponent range): the call WAITS for its kernel on `stream` to find out (a
+ * set-up call; LS_ERR_UNSUPPORTED on a capturing stream -- pack before a HIP-graph capture, never inside one). */
+int ls_linear_w4_pack(const uint8_t* q, const uint8_t* e, const uint8_t* q_up, const uint8_t* e_up, void* packed, int N,
+                      int K, int rope, void* stream);
+
+/* As ls_linear_workspace_bytes / ls_linear_fwd with d->w[i] pointing at 4-bit packed segments (d->dtype is the
+ * activation / output dtype); K % 64 == 0 and K >= 128.  The folded RMSNorm fields (norm_weight, ssq_in, ssq_out) are
+ * LS_ERR_UNSUPPORTED here, and there is no prefetch call. */
+size_t ls_linear_w4_workspace_bytes(const ls_linear_desc* d);
+int ls_linear_w4_fwd(const ls_linear_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- RMSNorm / RoPE (K8, K9) ------------------------------------------------ */
 
 /* LlamaRMSNorm.forward (transformers; imported at longspec/test/llama.py:36; vendored

@@ -80,6 +80,11 @@ SYMBOLS = {
     "ls_linear_w8_pack": (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "ls_linear_w8_workspace_bytes": (C.c_size_t, [C.POINTER(LinearDesc)]),
     "ls_linear_w8_fwd": (C.c_int, [C.POINTER(LinearDesc), C.POINTER(_P), _P, C.c_size_t, _P]),
+    "ls_linear_w4_packed_bytes": (C.c_size_t, [_I, _I]),
+    "ls_linear_w4_quantize": (C.c_int, [_P, _I, _I, _I, _P, _P, _P]),
+    "ls_linear_w4_pack": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "ls_linear_w4_workspace_bytes": (C.c_size_t, [C.POINTER(LinearDesc)]),
+    "ls_linear_w4_fwd": (C.c_int, [C.POINTER(LinearDesc), _P, C.c_size_t, _P]),
     "ls_topk_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "ls_logprob_topk": (C.c_int, [_P, _I, _I, _L, _I, _P, _I, _P, _P, _P, C.c_size_t, _P]),
     "ls_logprob_topk_store": (C.c_int, [_P, _I, _I, _L, _I, _P, _I, _P, _P, _P, _L, _P, C.c_size_t, _P]),

@@ -53,6 +53,7 @@ struct W16 {
     static constexpr bool SCALED = false;
     static constexpr bool FOLDED_NORM = true;
     static constexpr int CHUNK_BYTES = 2 * 4096;
+    static constexpr int TILE_BYTES = 1024, LANE_BYTES = 16;
     // M <= 16 / <= 32 / above with 64-row slabs: 4 / 3 / 3 chunks in flight per wave; 128-row slabs: 1 (16 KB)
     static constexpr int lac(int MT, int NT) { return NT == 8 ? 1 : MT == 1 ? 4 : 3; }
     template <typename E, int NT>

@@ -68,6 +68,7 @@ struct W8 {
     static constexpr bool SCALED = true;
     static constexpr bool FOLDED_NORM = false;
     static constexpr int CHUNK_BYTES = 4096;
+    static constexpr int TILE_BYTES = 1024, LANE_BYTES = 16;
     static constexpr int lac(int MT, int NT) { return NT == 8 ? 2 : MT == 1 ? 8 : 6; }
     template <typename E, int NT>
     struct Set {

@@ -1,12 +1,14 @@
-// skinny_gemm.h -- the ONE body of the weight-streaming skinny GEMM, shared by its two translation units:
+// skinny_gemm.h -- the ONE body of the weight-streaming skinny GEMM, shared by its three translation units:
 //   gemm.hip     16-bit weights (policy W16, kernel skinny_gemm_kernel)     -- the design is described in its header comment
 //   gemm_w8.hip  e4m3 weights   (policy W8,  kernel skinny_gemm_w8_kernel)
+//   gemm_w4.hip  MXFP4 weights  (policy W4,  kernel skinny_gemm_w4_kernel)
 // A weight-format policy `W` supplies exactly what the format changes; the segment / tile set-up, the x staging, the
 // steady-state and drain loops, the 4-wave reduction, the split-K last-arriver protocol and the epilogues exist once, so
 // "same plan, same k order, same rounding points in both formats" holds by construction.
 //
 //   W::Args                     kernel argument struct: GemmK, or GemmK with the row scales appended
 //   W::CHUNK_BYTES              bytes of one 64-k chunk of a 64-row group, the stride of the weight stream
+//   W::TILE_BYTES, LANE_BYTES   inside a chunk: tile t's block starts at t * TILE_BYTES, lane l's bytes at l * LANE_BYTES
 //   W::lac(MT, NT)              chunks of look-ahead per wave
 //   W::Set<E, NT>               the registers of one chunk of the workgroup's NT tiles
 //   W::issue<E, NT>(set, wtile, ks0)          request the chunk that starts at k-step ks0 (non-temporal in both formats)
@@ -18,7 +20,7 @@
 #pragma once
 #include "ls_common.h"
 
-// (An anonymous namespace in a header, on purpose: this header is the shared part of exactly two translation units whose
+// (An anonymous namespace in a header, on purpose: this header is the shared part of exactly three translation units whose
 // own contents are anonymous too, and the kernels' mangled names -- which tools and tests match -- contain it.)
 namespace {
 
@@ -104,7 +106,7 @@ __device__ __forceinline__ void skinny_gemm_body(const typename W::Args& args) {
     const int ch_end = (int)(((long)nch_all * (split + 1)) / p.S);
 
     // ---- the NT weight tiles of this workgroup.  The 64-k chunk c of 64-row group g starts at (g * K/64 + c) * CHUNK_BYTES
-    // and is made of 1 KB blocks, those of the group's 4 tiles adjacent (which blocks: the policy's translation unit).
+    // and is made of TILE_BYTES blocks, those of the group's 4 tiles adjacent (which blocks: the policy's translation unit).
     // EPI_SILU_MUL: the packed matrix alternates gate and up tiles (tile 2j = gate rows 16j.., tile 2j+1 = up rows
     // 16j..), so tiles (2j, 2j+1) make output columns 16j..16j+15.
     // EPI_QKV_ROPE: like EPI_NONE, but the q and k segments are packed in rope order (within each 128-row
@@ -131,7 +133,7 @@ __device__ __forceinline__ void skinny_gemm_body(const typename W::Args& args) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const int g = min(((row0 - seg_base) >> 6) + (t >> 2), ngroups - 1);    // clamp: tiles past the end are never stored
-            wtile[t] = p.w[seg] + (long)g * group_b + (t & 3) * 1024 + lane * 16;
+            wtile[t] = p.w[seg] + (long)g * group_b + (t & 3) * W::TILE_BYTES + lane * W::LANE_BYTES;
         }
     }
 
@@ -461,7 +463,7 @@ __device__ __forceinline__ void skinny_gemm_body(const typename W::Args& args) {
     }
 }
 
-// ---- weight packing: the tile permutation both packers share.  Packed 16-row tile T, lane l holds a row of `w`, or of
+// ---- weight packing: the tile permutation all packers share.  Packed 16-row tile T, lane l holds a row of `w`, or of
 // `w_up`: a gate/up pair is packed as ONE matrix of 2N rows whose tiles alternate (tile 2j = gate rows 16j.., tile 2j+1 =
 // up rows 16j..: the silu(gate)*up epilogue pairs neighbouring tiles).  `rope` packs a q/k projection for EPI_QKV_ROPE:
 // within every 128-row head the 8 tiles are stored in the order 0,4,1,5,2,6,3,7, so that rows d.. and 64+d.. (a rotary

@@ -82,15 +82,24 @@ class LlamaRMSNorm(nn.Module):
         return self.ops.rmsnorm(hidden_states, self.weight, self.variance_epsilon)
 
 
-WEIGHT_QUANT_ENV = "LONGSPEC_WEIGHT_QUANT"     # "fp8": every projection, "fp8-draft": the draft layer only; unset: 16-bit
-_ENV_SCOPES = {"fp8": ("draft", "target"), "fp8-draft": ("draft",)}
+WEIGHT_QUANT_ENV = "LONGSPEC_WEIGHT_QUANT"     # "fp8" / "fp4": every projection, "fp8-draft" / "fp4-draft": the draft layer only; unset: 16-bit
+_ENV_SCOPES = {"fp8": ("draft", "target"), "fp8-draft": ("draft",), "fp4": ("draft", "target"), "fp4-draft": ("draft",)}
+WEIGHT_FORMATS = ("fp8", "mxfp4")
 
 
-def _env_quant_scopes():
+def _env_quant_mode():
     mode = os.environ.get(WEIGHT_QUANT_ENV, "")
     if mode and mode not in _ENV_SCOPES:
         raise ValueError(f"{WEIGHT_QUANT_ENV}={mode!r}: expected one of {sorted(_ENV_SCOPES)}")
-    return _ENV_SCOPES.get(mode, ())
+    return mode
+
+
+def _env_quant_scopes():
+    return _ENV_SCOPES.get(_env_quant_mode(), ())
+
+
+def _env_quant_fmt() -> str:
+    return "mxfp4" if _env_quant_mode().startswith("fp4") else "fp8"
 
 
 class DecodeLinear(nn.Linear):
@@ -98,9 +107,10 @@ class DecodeLinear(nn.Linear):
     streams a packed copy of the weight (MFMA operand order, built once per weight version) through
     ``ops.linear``; anything else is ``F.linear``.
 
-    Weight mode ``weight_quant``: ``None`` (16-bit) or ``"fp8"`` (``quantize_weight_``): ``.weight`` then holds the
-    e4m3-rounded values ``q * 2^e`` -- exact in fp16 / bf16 -- and the decode-shaped path streams the 8-bit pack of the
-    same numbers, so both paths of the module (and a 16-bit module loaded from its state_dict) compute the same thing."""
+    Weight mode ``weight_quant``: ``None`` (16-bit), ``"fp8"`` or ``"mxfp4"`` (``quantize_weight_``): ``.weight`` then holds
+    the rounded values (e4m3 ``q * 2^e`` per row, or e2m1 ``q * 2^e`` per 32-k block) -- exact in fp16 / bf16 -- and the
+    decode-shaped path streams the 8-bit / 4-bit pack of the same numbers, so both paths of the module (and a 16-bit module
+    loaded from its state_dict) compute the same thing."""
 
     def __init__(self, in_features, out_features, bias=True, ops=None):
         super().__init__(in_features, out_features, bias=bias)
@@ -110,30 +120,45 @@ class DecodeLinear(nn.Linear):
         self.weight_quant = None
         self.quant_scope = "target"          # "draft" for the projections of the draft layer (set by the owning model)
         self._q8 = None                      # (q uint8 [N, K], scale fp32 [N]) of the current weight version (GPU only)
+        self._q4 = None                      # (q uint8 [N, K/2], e uint8 [N, K/32]), likewise, for "mxfp4"
         self._env_scopes = _env_quant_scopes()
+        self._env_fmt = _env_quant_fmt()
 
     def _key(self):
         w = self.weight
         return (w.data_ptr(), w._version, w.dtype, w.device)
 
     @torch.no_grad()
-    def quantize_weight_(self):
-        """Round the weight to the e4m3 grid with one power-of-two scale per row (quant.py) and write the de-quantised
-        values back into ``.weight``.  On the GPU the bytes and scales are kept for the 8-bit pack."""
+    def quantize_weight_(self, fmt: Optional[str] = None):
+        """Round the weight and write the de-quantised values back into ``.weight`` (quant.py).  ``fmt="fp8"``: the e4m3 grid
+        with one power-of-two scale per row; ``fmt="mxfp4"``: the e2m1 grid with one power-of-two scale per 32-k block.
+        ``None``: the format the module already has, else the process-wide default's (LONGSPEC_WEIGHT_QUANT), else "fp8".
+        On the GPU the quantised form is kept for the 8-bit / 4-bit pack."""
         from . import quant
+        if fmt is None:
+            fmt = self.weight_quant or self._env_fmt
+        if fmt not in WEIGHT_FORMATS:
+            raise ValueError(f"quantize_weight_: format {fmt!r} is not one of {WEIGHT_FORMATS}")
         w = self.weight
-        on_gpu = w.is_cuda and hasattr(self.ops, "quantize_rows_e4m3") and w.dtype in (torch.float16, torch.bfloat16) \
-            and self.in_features % 8 == 0
-        q, scale = self.ops.quantize_rows_e4m3(w) if on_gpu else quant.quantize_rows_e4m3(w)
-        w.copy_(quant.dequantize_rows_e4m3(q, scale, w.dtype))
-        self._q8 = (q, scale) if on_gpu else None
-        self.weight_quant = "fp8"
+        dev_ok = w.is_cuda and w.dtype in (torch.float16, torch.bfloat16)
+        self._q8 = self._q4 = None
+        if fmt == "mxfp4":
+            on_gpu = dev_ok and hasattr(self.ops, "quantize_blocks_mxfp4") and self.in_features % 32 == 0
+            q, e = self.ops.quantize_blocks_mxfp4(w) if on_gpu else quant.quantize_blocks_mxfp4(w)
+            w.copy_(quant.dequantize_blocks_mxfp4(q, e, w.dtype))
+            self._q4 = (q, e) if on_gpu else None
+        else:
+            on_gpu = dev_ok and hasattr(self.ops, "quantize_rows_e4m3") and self.in_features % 8 == 0
+            q, scale = self.ops.quantize_rows_e4m3(w) if on_gpu else quant.quantize_rows_e4m3(w)
+            w.copy_(quant.dequantize_rows_e4m3(q, scale, w.dtype))
+            self._q8 = (q, scale) if on_gpu else None
+        self.weight_quant = fmt
         self._packed = {}
         self._packed_key = self._key()
         return self
 
     def _quant_due(self) -> bool:
-        """The weight is (to be) kept on the e4m3 grid and has changed since it was last rounded.  The process-wide default
+        """The weight is (to be) kept on its quantisation grid and has changed since it was last rounded.  The process-wide default
         (LONGSPEC_WEIGHT_QUANT) is honoured here, at the first use, because a benchmark may fill the weights in place after
         constructing the model."""
         return (self.weight_quant is not None or self.quant_scope in self._env_scopes) and self._packed_key != self._key()
@@ -148,9 +173,11 @@ class DecodeLinear(nn.Linear):
                 self._packed, self._packed_key = {}, key
         if rope not in self._packed:
             if self.weight_quant is not None:
-                if self._q8 is None:
-                    raise RuntimeError("DecodeLinear: an fp8 weight streams through the HIP operator layer only (fp16 / bf16 on the GPU)")
-                self._packed[rope] = self.ops.pack_weight8(self._q8, rope=rope)
+                if self._q8 is None and self._q4 is None:
+                    raise RuntimeError(f"DecodeLinear: an {self.weight_quant} weight streams through the HIP operator layer only "
+                                       "(fp16 / bf16 on the GPU)")
+                self._packed[rope] = (self.ops.pack_weight4(self._q4, rope=rope) if self.weight_quant == "mxfp4"
+                                      else self.ops.pack_weight8(self._q8, rope=rope))
             else:
                 self._packed[rope] = self.ops.pack_weight(self.weight, rope=True) if rope else self.ops.pack_weight(self.weight)
         return self._packed[rope]
@@ -204,7 +231,9 @@ class LlamaMLP(nn.Module):
         g, u = gp.weight, up.weight
         key = (g.data_ptr(), g._version, u.data_ptr(), u._version, g.dtype, g.device, gp.weight_quant, up.weight_quant)
         if self._gate_up_key != key:
-            if gp.weight_quant is not None and up.weight_quant is not None:
+            if gp.weight_quant == "mxfp4" and up.weight_quant == "mxfp4":
+                self._gate_up = self.ops.pack_gate_up4(gp._q4, up._q4)
+            elif gp.weight_quant == "fp8" and up.weight_quant == "fp8":
                 self._gate_up = self.ops.pack_gate_up8(gp._q8, up._q8)
             else:
                 self._gate_up = self.ops.pack_gate_up(g, u)
@@ -521,20 +550,26 @@ class LlamaForCausalLM(nn.Module):
     QUANT_SCOPES = {"target": ("target",), "draft": ("draft",), "all": ("draft", "target")}
 
     @torch.no_grad()
-    def quantize_weights_(self, scope: str = "all"):
-        """FP8 (e4m3) weights for the decode projections (no counterpart in the reference).  ``scope``: ``"target"`` (the
-        decoder layers' q/k/v/o and MLP projections and the lm_head -- which the draft passes share), ``"draft"`` (the
-        projections of the draft layer; lossless with respect to the 16-bit target, which still verifies every token) or
-        ``"all"``.  Embeddings and norms are never quantised.
+    def quantize_weights_(self, scope: str = "all", fmt: str = "fp8"):
+        """FP8 (e4m3) or MXFP4 (e2m1, 32-k blocks) weights for the decode projections (no counterpart in the reference).
+        ``scope``: ``"target"`` (the decoder layers' q/k/v/o and MLP projections and the lm_head -- which the draft passes
+        share), ``"draft"`` (the projections of the draft layer; lossless with respect to the 16-bit target, which still
+        verifies every token) or ``"all"``.  Embeddings and norms are never quantised.
 
-        Every projection in scope has its weight rounded to the e4m3 grid with a power-of-two scale per output row
-        (``quant.py``); the de-quantised values -- exact in fp16 / bf16 -- are written back into ``.weight`` and, on the
-        GPU, the decode-shaped path streams the 8-bit pack.  Prefill-shaped calls keep multiplying ``.weight``, and so does
-        the vocabulary-sharded lm_head slice (``dist.KVShard.head_select``), which stays 16-bit: the same numbers.  The model
-        is therefore the 16-bit model with these weights, token for token.  On the CPU only ``.weight`` is rewritten."""
+        Every projection in scope has its weight rounded to nearest on the format's grid -- ``"fp8"``: e4m3 with a
+        power-of-two scale per output row; ``"mxfp4"``: e2m1 with a power-of-two scale per 32 consecutive k (``quant.py``) --
+        and the de-quantised values, exact in fp16 / bf16, are written back into ``.weight``; on the GPU the decode-shaped
+        path streams the 8-bit / 4-bit pack.  Prefill-shaped calls keep multiplying ``.weight``, and so does the
+        vocabulary-sharded lm_head slice (``dist.KVShard.head_select``), which stays 16-bit: the same numbers.  The model is
+        therefore the 16-bit model with these weights, token for token.  On the CPU only ``.weight`` is rewritten.
+
+        What the rounding does to the model's quality is the caller's business: round-to-nearest 4-bit weights on the target
+        scope are a lossy model."""
         if scope not in self.QUANT_SCOPES:
             raise ValueError(f"quantize_weights_: scope {scope!r} is not one of {sorted(self.QUANT_SCOPES)}")
+        if fmt not in WEIGHT_FORMATS:
+            raise ValueError(f"quantize_weights_: format {fmt!r} is not one of {WEIGHT_FORMATS}")
         for m in self.modules():
             if isinstance(m, DecodeLinear) and m.quant_scope in self.QUANT_SCOPES[scope]:
-                m.quantize_weight_()
+                m.quantize_weight_(fmt)
         return self

@@ -190,6 +190,18 @@ class _DecodeState(SimpleNamespace):
     graph_captures = property(lambda self: self.replayer.captures)
 
 
+DRAFT_HEAD_ENV = "LONGSPEC_DRAFT_HEAD"         # "fp8" / "fp4": quantize_draft_head_ at the first draft pass; unset: the shared lm_head
+_ENV_DRAFT_HEAD = {"fp8": "fp8", "fp4": "mxfp4"}
+
+
+def _env_draft_head():
+    import os
+    mode = os.environ.get(DRAFT_HEAD_ENV, "")
+    if mode and mode not in _ENV_DRAFT_HEAD:
+        raise ValueError(f"{DRAFT_HEAD_ENV}={mode!r}: expected one of {sorted(_ENV_DRAFT_HEAD)}")
+    return _ENV_DRAFT_HEAD.get(mode)
+
+
 def _sync(t: torch.Tensor):
     if t.is_cuda:
         torch.cuda.synchronize(t.device)
@@ -213,7 +225,10 @@ class LlamaGlide(LlamaForCausalLM):
         self.glide = self.GLIDE_LAYER_CLS(config, ops=self.ops)
         for m in self.glide.modules():
             if isinstance(m, DecodeLinear):
-                m.quant_scope = "draft"        # quantize_weights_("draft") / LONGSPEC_WEIGHT_QUANT=fp8-draft
+                m.quant_scope = "draft"        # quantize_weights_("draft") / LONGSPEC_WEIGHT_QUANT=fp8-draft, fp4-draft
+        self.draft_lm_head = None              # quantize_draft_head_ / LONGSPEC_DRAFT_HEAD: the draft passes' own lm_head
+        self._draft_head_env = _env_draft_head()
+        self._draft_head_env_key = None
         if target_model_path is not None or glide_path is not None:
             from .checkpoint import load_draft_checkpoint, load_target_checkpoint
             if target_model_path is not None:
@@ -241,6 +256,64 @@ class LlamaGlide(LlamaForCausalLM):
                              # budget instead made a 1k-token prompt with a 20k budget run 21k-row launch shapes from round 1.
 
     # ------------------------------------------------------------------------------------------
+    def __setattr__(self, name, value):
+        # the draft head is NOT a registered sub-module: parameters(), state_dict() and .to() do not see it
+        if name == "draft_lm_head":
+            if value is not None and not isinstance(value, DecodeLinear):
+                raise TypeError("draft_lm_head is a DecodeLinear or None")
+            object.__setattr__(self, name, value)
+        else:
+            super().__setattr__(name, value)
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to() / .half() / .cuda(): the unregistered draft head follows the model (its pack is rebuilt, and the weight rounded
+        # again -- to the same values -- at its next use: DecodeLinear keys both on the weight's device, dtype and version)
+        out = super()._apply(fn, *args, **kwargs)
+        head = getattr(self, "draft_lm_head", None)
+        if head is not None:
+            head._apply(fn, *args, **kwargs)
+        return out
+
+    @torch.no_grad()
+    def quantize_draft_head_(self, fmt: str = "fp8"):
+        """A low-precision copy of the lm_head for the DRAFT passes only (no counterpart in the reference): ``draft_lm_head``
+        becomes a ``DecodeLinear`` that holds ``lm_head.weight`` as it is now, rounded to ``fmt`` (``"fp8"`` or ``"mxfp4"``,
+        ``DecodeLinear.quantize_weight_``), and streams the 8-bit / 4-bit pack.  ``lm_head`` itself is not touched and the
+        copy is not a registered module (``state_dict()`` keeps its keys).
+
+        Used by the lm_head calls of the glide draft passes: the tree rounds' step-0 and level calls and the chain drafter's
+        calls.  It changes what the draft proposes, and with it the acceptance length, never what the target accepts:
+        prefill's first token, every verify pass, ``vanilla_generate`` and MagicDec's self-draft keep multiplying
+        ``lm_head``, and so does the vocabulary-sharded ``head_select`` path (16-bit, draft passes included).
+        ``model.draft_lm_head = None`` restores the shared head.  ``model.to(...)`` / ``.half()`` / ``.cuda()`` move the copy
+        with the model (``_apply``), although ``parameters()`` and ``state_dict()`` do not list it."""
+        src = self.lm_head
+        # (the generate loops run under inference_mode: the copy must be an ordinary tensor, whose version DecodeLinear tracks)
+        with torch.inference_mode(False), torch.no_grad():
+            if src._quant_due():
+                src.quantize_weight_()
+            with torch.device("meta"):         # (no [vocab, hidden] fp32 initialisation on the host: the parameters follow)
+                head = DecodeLinear(src.in_features, src.out_features, bias=src.bias is not None, ops=self.ops)
+            head.weight = torch.nn.Parameter(src.weight.detach().clone(), requires_grad=False)
+            if src.bias is not None:
+                head.bias = torch.nn.Parameter(src.bias.detach().clone(), requires_grad=False)
+            head._env_scopes = ()              # the copy's format is this call's, not the process-wide default's
+            head.quantize_weight_(fmt)
+            if head.weight.is_cuda and (head._q8 is not None or head._q4 is not None):
+                head.packed()                  # before the first warm-up round: a captured graph only replays launches
+        self.draft_lm_head = head
+        return self
+
+    def _head_of_draft_passes(self):
+        """The lm_head of the glide draft passes: ``draft_lm_head`` when set (``quantize_draft_head_``, or built here at the
+        first use under LONGSPEC_DRAFT_HEAD -- a benchmark may fill the weights in place after constructing the model --
+        and again when ``lm_head.weight`` has changed since), else ``lm_head``."""
+        if self._draft_head_env and self._draft_head_env_key != self.lm_head._key():
+            if self.draft_lm_head is None or self._draft_head_env_key is not None:     # (never over a head the caller set)
+                self.quantize_draft_head_(self._draft_head_env)
+                self._draft_head_env_key = self.lm_head._key()
+        return self.draft_lm_head if self.draft_lm_head is not None else self.lm_head
+
     def set_max_gen_len(self, max_gen_len):
         super().set_max_gen_len(max_gen_len)
 
@@ -439,6 +512,8 @@ class LlamaGlide(LlamaForCausalLM):
         that time ``chain_round`` on synthetic KV (bench.py --method seq)."""
         bsz = first_token.size(0)
         dev = first_token.device
+        if drafter != "magicdec":
+            self._head_of_draft_passes()                # the draft passes' head and its pack exist before the first round
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
                              max_gen_len=max_gen_len, count=0, num=0, emitted=1, double_flag=False)
         st.output_ids = first_token.new_zeros((bsz, max_gen_len + gamma))
@@ -471,6 +546,7 @@ class LlamaGlide(LlamaForCausalLM):
         spec_buffer, spec_logits, next_spec_start_token = st.spec_buffer, st.spec_logits, st.next_spec_start_token
         bound = P + st.emitted + gamma + 2
         self._set_hints(bound, bound)
+        draft_head = self.lm_head if magic else self._head_of_draft_passes()      # MagicDec: the target drafts with its own head
         for spec_steps in range(0, gamma):
             if spec_steps == 0:
                 if st.double_flag:
@@ -500,13 +576,13 @@ class LlamaGlide(LlamaForCausalLM):
                                            llm_kv_len=cache_lens, exec_type="decoding", prenormed=prenormed)
             if st.double_flag and spec_steps == 0:
                 draft_cache_lens += 2                    # 1 + double_input (batch 1: the host knows the flag)
-                current_logp = self.lm_head(hidden_states[:, -2:, :])
+                current_logp = draft_head(hidden_states[:, -2:, :])
                 spec_buffer[:, spec_steps + 1] = self.ops.argmax_rows(current_logp)[:, 1]
                 if spec_logits is not None:
                     spec_logits[:, spec_steps + 1, :] = current_logp[:, 1, :]
             else:
                 draft_cache_lens += 1
-                current_logp = self.lm_head(hidden_states[:, -1, :])
+                current_logp = draft_head(hidden_states[:, -1, :])
                 spec_buffer[:, spec_steps + 1] = self.ops.argmax_rows(current_logp).view(-1,)
                 if spec_logits is not None:
                     spec_logits[:, spec_steps + 1, :] = current_logp
@@ -629,6 +705,7 @@ class LlamaGlide(LlamaForCausalLM):
         Fn = acc_n[-1]                       # tree nodes incl. the root
         gamma = len(cand)
         R = Fn - 1 + gamma + 1               # verification rows: [a accepted | F-1 tree | pads]
+        self._head_of_draft_passes()                    # the draft passes' head and its pack exist before the first warm-up round
         st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz)
         st.output_ids = torch.full((bsz, max_gen_len), self._tree_output_fill(eos_id), dtype=torch.int64, device=dev)  # :937 (G8)
         st.spec_mask = torch.zeros((bsz, max_gen_len), dtype=torch.int64, device=dev)
@@ -779,10 +856,11 @@ class LlamaGlide(LlamaForCausalLM):
         # with `vocab_parallel` every rank multiplies by its slice of the lm_head only (dist.KVShard.head_select)
         vsh = last_attn.shard if (last_attn.shard is not None and last_attn.shard.vocab_parallel and st.temperature == 0) else None
         vocab_size = self.lm_head.out_features
+        draft_head = self._head_of_draft_passes()             # (the vocabulary-sharded head_select path stays on the 16-bit lm_head)
         if vsh is not None:
             topk_logp, pred_ids = vsh.head_select(self.lm_head, hidden_states[:, a - 1, :], ops, k=cand[0])
         else:
-            logits = self.lm_head(hidden_states[:, a - 1, :]).view(bsz, 1, -1)
+            logits = draft_head(hidden_states[:, a - 1, :]).view(bsz, 1, -1)
             if st.temperature > 0:                     # spec_logits[:, 0] = current_logp (:1025, G8: log-probs, not logits)
                 if st.spec_logits is None:
                     st.spec_logits = torch.zeros((bsz, Fn, vocab_size), dtype=torch.float32, device=logits.device)
@@ -809,7 +887,7 @@ class LlamaGlide(LlamaForCausalLM):
                 topk_logp_sum, topk_indices = vsh.head_select(self.lm_head, hidden_states, ops, k=cand[ms],
                                                               history=history_logp_sum[:, lo:mid])
             else:
-                level_logits = self.lm_head(hidden_states)
+                level_logits = draft_head(hidden_states)
                 if st.temperature > 0 and st.fused_logp:
                     topk_logp_sum, topk_indices = ops.logprob_topk(level_logits, history_logp_sum[:, lo:mid], cand[ms],
                                                                    logp_out=st.spec_logits[:, lo:mid])

@@ -14,7 +14,7 @@ One function per reference seam of the draft-then-verify round:
   tree_commit / tree_commit_stochastic   end of a round at temperature 0 / > 0  llama_glide.py:1093-1121
   linear / linear_multi / mlp_gate_up   the projections of a decode pass (M <= 80 token rows):
                          q/k/v/o_proj llama.py:361-363,390, LlamaMLP (qwen2.py:218-230), lm_head llama_glide.py:1091
-                         -- with 16-bit (pack_weight) or 8-bit e4m3 (pack_weight8) packed weights
+                         -- with 16-bit (pack_weight), 8-bit e4m3 (pack_weight8) or 4-bit MXFP4 (pack_weight4) packed weights
 
 Everything runs on the CURRENT torch stream, without host synchronisation.  There is
 no fallback: a missing extension or a CPU tensor raises.
@@ -223,6 +223,75 @@ def pack_gate_up8(gate_weight, up_weight) -> PackedWeight8:
     return PackedWeight8(out, torch.stack([sg, su]).contiguous(), N, K, pair=True)
 
 
+class PackedWeight4:
+    """A weight [N, K] as OCP MX FP4 (e2m1 nibbles, one e8m0 scale byte per 32 k of a row) in the streamed 4-bit layout
+    (``ls_linear_w4_pack``, include/longspec_hip.h): ``data`` is a flat uint8 tensor of ceil(N/64) * (K/64) * 2176 bytes
+    that holds the scale bytes too.  ``dtype`` is always ``torch.uint8``: the activation dtype is the caller's."""
+    __slots__ = ("data", "n", "k", "dtype", "rope", "pair")
+
+    def __init__(self, data, n, k, rope=False, pair=False):
+        self.data, self.n, self.k, self.dtype, self.rope, self.pair = data, n, k, torch.uint8, rope, pair
+
+
+W4_CALLS = 0          # launches of ls_linear_w4_fwd so far (tests assert that a quantised model really streams 4-bit weights)
+
+
+def quantize_blocks_mxfp4(weight: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Device twin of ``quant.quantize_blocks_mxfp4`` (bit-identical): fp16 / bf16 [N, K] -> (q uint8 [N, K/2], e uint8
+    [N, K/32])."""
+    _dev(weight)
+    if weight.dim() != 2 or weight.shape[1] % 32 != 0 or weight.shape[1] == 0:
+        raise ValueError("quantize_blocks_mxfp4: [N, K] weight with K a multiple of 32 expected")
+    w = weight.detach().contiguous()
+    N, K = w.shape
+    q = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    e = torch.empty((N, K // 32), dtype=torch.uint8, device=w.device)
+    _C.check(_C.load().ls_linear_w4_quantize(w.data_ptr(), N, K, _dtype(w), q.data_ptr(), e.data_ptr(), _stream()),
+             "ls_linear_w4_quantize")
+    return q, e
+
+
+def _as_q_e(weight):
+    """``weight``: a 16-bit [N, K] tensor (quantised here) or a pre-quantised ``(q uint8 [N, K/2], e uint8 [N, K/32])`` pair
+    (an MXFP4 checkpoint quantised elsewhere; its exponent bytes must lie in [114, 140], ``ls_linear_w4_pack`` checks)."""
+    if isinstance(weight, (tuple, list)):
+        q, e = weight
+        _dev(q, e)
+        if (q.dtype != torch.uint8 or e.dtype != torch.uint8 or q.dim() != 2 or e.dim() != 2 or q.shape[0] != e.shape[0]
+                or q.shape[1] != e.shape[1] * 16):
+            raise ValueError("pack_weight4: a pre-quantised weight is (q uint8 [N, K/2], e uint8 [N, K/32])")
+        return q.contiguous(), e.contiguous()
+    return quantize_blocks_mxfp4(weight)
+
+
+def pack_weight4(weight, rope: bool = False) -> PackedWeight4:
+    """Quantise (unless ``weight`` is already a ``(q, e)`` pair) and pack for the 4-bit skinny GEMM.  ``rope=True``: the
+    q/k layout of ``linear_qkv_rope``."""
+    q, e = _as_q_e(weight)
+    N, K = q.shape[0], q.shape[1] * 2
+    if K % 64 != 0 or K < 128 or (rope and N % 128 != 0):
+        raise ValueError("pack_weight4: K must be a multiple of 64 (>= 128); rope=True needs N = heads x 128")
+    lib = _C.load()
+    out = torch.empty(lib.ls_linear_w4_packed_bytes(N, K), dtype=torch.uint8, device=q.device)
+    _C.check(lib.ls_linear_w4_pack(q.data_ptr(), e.data_ptr(), None, None, out.data_ptr(), N, K, int(rope), _stream()),
+             "ls_linear_w4_pack")
+    return PackedWeight4(out, N, K, rope=rope)
+
+
+def pack_gate_up4(gate_weight, up_weight) -> PackedWeight4:
+    """gate_proj / up_proj of one MLP (16-bit tensors or ``(q, e)`` pairs) as one 4-bit packed matrix with alternating
+    16-row tiles: the operand of ``mlp_gate_up``."""
+    (qg, eg), (qu, eu) = _as_q_e(gate_weight), _as_q_e(up_weight)
+    if qg.shape != qu.shape or qg.shape[0] % 16 or qg.shape[1] % 32 or qg.shape[1] < 64:
+        raise ValueError("pack_gate_up4: two [N, K] weights with N % 16 == 0 and K % 64 == 0 (>= 128) expected")
+    N, K = qg.shape[0], qg.shape[1] * 2
+    lib = _C.load()
+    out = torch.empty(lib.ls_linear_w4_packed_bytes(2 * N, K), dtype=torch.uint8, device=qg.device)
+    _C.check(lib.ls_linear_w4_pack(qg.data_ptr(), eg.data_ptr(), qu.data_ptr(), eu.data_ptr(), out.data_ptr(), N, K, 0, _stream()),
+             "ls_linear_w4_pack")
+    return PackedWeight4(out, N, K, pair=True)
+
+
 def logprob_topk(logits: torch.Tensor, history: Optional[torch.Tensor], k: int,
                  logp_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(logits.float().log_softmax(-1) + history[..., None]).view(bsz, -1).topk(k)`` (llama_glide.py:1019-1020,
@@ -352,6 +421,9 @@ class NormFold:
 PREFETCH_PROBE = 0       # measurement switch (tools/bench_l2_prefetch.py), 0 in the product
 
 
+_PACK_BITS = {PackedWeight: 16, PackedWeight8: 8, PackedWeight4: 4}
+
+
 def _linear_call(x, weights, biases, epilogue, n_splits=0, timing=None, rope=None, residual=None, norm=None, ssq_out=False):
     _dev(x)
     K = x.shape[-1]
@@ -362,21 +434,25 @@ def _linear_call(x, weights, biases, epilogue, n_splits=0, timing=None, rope=Non
     d = _C.LinearDesc()
     d.x = x2.data_ptr()
     n_tot = 0
-    w8 = isinstance(weights[0], PackedWeight8)
-    if w8:
-        if any(not isinstance(w, PackedWeight8) for w in weights):
-            raise ValueError("linear: the segments of one call are all 8-bit or all 16-bit packed weights")
+    cls = type(weights[0])
+    w8, w4 = cls is PackedWeight8, cls is PackedWeight4
+    if cls not in _PACK_BITS:
+        raise TypeError("linear: weights must be PackedWeight (ops.pack_weight(nn.Linear.weight)), PackedWeight8 or PackedWeight4")
+    if any(type(w) in _PACK_BITS and type(w) is not cls for w in weights):
+        raise ValueError("linear: one weight format per launch -- the segments of one call are all 4-bit, all 8-bit or all 16-bit "
+                         "packed weights")
+    if w8 or w4:
+        bits = _PACK_BITS[cls]
         if norm is not None or ssq_out:
-            raise ValueError("linear: the folded RMSNorm (norm=, ssq_out=) is not available with 8-bit weights")
+            raise ValueError(f"linear: the folded RMSNorm (norm=, ssq_out=) is not available with {bits}-bit weights")
         if weights[0].pair != (epilogue == _C.LS_EPI_SILU_MUL):
-            raise ValueError("linear: mlp_gate_up takes pack_gate_up8(...), every other call pack_weight8(...)")
-        scales = (C.c_void_p * 3)()
+            raise ValueError(f"linear: mlp_gate_up takes pack_gate_up{bits}(...), every other call pack_weight{bits}(...)")
+        if w8:
+            scales = (C.c_void_p * 3)()
     for i, w in enumerate(weights):
-        if not isinstance(w, (PackedWeight8 if w8 else PackedWeight)):
-            if isinstance(w, PackedWeight8):
-                raise ValueError("linear: the segments of one call are all 8-bit or all 16-bit packed weights")
-            raise TypeError("linear: weights must be PackedWeight (ops.pack_weight(nn.Linear.weight))")
-        if w.k != K or (not w8 and w.dtype != x.dtype):
+        if type(w) is not cls:
+            raise TypeError("linear: weights must be PackedWeight (ops.pack_weight(nn.Linear.weight)), PackedWeight8 or PackedWeight4")
+        if w.k != K or (cls is PackedWeight and w.dtype != x.dtype):
             raise ValueError(f"packed weight [{w.n}, {w.k}] {w.dtype} does not match x [..., {K}] {x.dtype}")
         if w8:
             if w.pair:
@@ -429,15 +505,19 @@ def _linear_call(x, weights, biases, epilogue, n_splits=0, timing=None, rope=Non
         d.ssq_out = ssq.data_ptr()
     if timing is None and _linear_timing is not None:
         rows_w = sum(w.n for w in weights) * (2 if epilogue == _C.LS_EPI_SILU_MUL else 1)
-        timing = _linear_timing(rows_w * K * (1 if w8 else x.element_size()) + (M * K + M * n_out) * x.element_size())
+        w_bytes = rows_w * K if w8 else rows_w * K * 17 // 32 if w4 else rows_w * K * x.element_size()
+        timing = _linear_timing(w_bytes + (M * K + M * n_out) * x.element_size())
     if timing is not None:          # (torch.cuda.Event, torch.cuda.Event), both already created by a record()
         d.ev_start, d.ev_stop = timing[0].cuda_event, timing[1].cuda_event
     lib = _C.load()
-    key = (M, K, d.n[0], d.n[1], d.n[2], epilogue, n_splits, d.dtype, norm is not None, w8)
+    key = (M, K, d.n[0], d.n[1], d.n[2], epilogue, n_splits, d.dtype, norm is not None, _PACK_BITS[cls])
     need = _linear_need.get(key)
     if need is None:
-        need = lib.ls_linear_w8_workspace_bytes(C.byref(d)) if w8 else lib.ls_linear_workspace_bytes(C.byref(d))
+        need = (lib.ls_linear_w8_workspace_bytes(C.byref(d)) if w8 else lib.ls_linear_w4_workspace_bytes(C.byref(d)) if w4
+                else lib.ls_linear_workspace_bytes(C.byref(d)))
         if need == 0:                                                                          # raises with the reason
+            if w4:
+                _C.check(lib.ls_linear_w4_fwd(C.byref(d), None, 0, _stream()), "ls_linear_w4_fwd")
             if w8:
                 _C.check(lib.ls_linear_w8_fwd(C.byref(d), scales, None, 0, _stream()), "ls_linear_w8_fwd")
             _C.check(lib.ls_linear_fwd(C.byref(d), None, 0, _stream()), "ls_linear_fwd")
@@ -448,6 +528,11 @@ def _linear_call(x, weights, biases, epilogue, n_splits=0, timing=None, rope=Non
         global W8_CALLS
         _C.check(lib.ls_linear_w8_fwd(C.byref(d), scales, ws.data_ptr(), ws.numel(), stream), "ls_linear_w8_fwd")
         W8_CALLS += 1
+        return y
+    if w4:
+        global W4_CALLS
+        _C.check(lib.ls_linear_w4_fwd(C.byref(d), ws.data_ptr(), ws.numel(), stream), "ls_linear_w4_fwd")
+        W4_CALLS += 1
         return y
     if PREFETCH_PROBE > 0:          # tools/bench_l2_prefetch.py: what an L2-resident head of the weight stream is worth
         ev = (d.ev_start, d.ev_stop)
