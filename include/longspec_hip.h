@@ -338,6 +338,27 @@ int ls_logprob_topk_store(const void* logits, int rows, int vocab, int64_t ld, i
 int ls_argmax_rows(const void* logits, int rows, int vocab, int64_t ld, int dtype, int64_t* out_idx,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* Scratch for ls_sample_rows (per-row selection state, per-chunk histograms and candidates). */
+size_t ls_sample_workspace_bytes(int rows, int vocab);
+
+/* One draw per row from soft-max(x / temperature) restricted by top-k and top-p (no counterpart in the reference, whose
+ * temperature > 0 paths are ls_tree_verify_stochastic and the chain's rejection block): logits [rows, vocab] dtype (row
+ * stride ld; vocab and ld multiples of 8, 16-byte aligned), positions [rows] int64 and streams [rows] int32 (NULL = 0) on the
+ * device.  The kept set is {x_j >= t}: top_k > 0 keeps the k largest values counted with multiplicity (ties at the k-th
+ * value all kept); top_p < 1 then keeps, of those, the values down to the largest v whose mass from the top,
+ * sum n(v') exp((v' - x_max) / temperature) over v' >= v, reaches top_p of the kept mass.  A -inf logit is kept only in a row
+ * without a finite one.  The draw is the Gumbel-max with Philox4x32-10, key (seed lo, seed hi), counter (j >> 2, position lo,
+ * position hi, stream), output word j & 3 = w_j:  u_j = ((w_j >> 9) + 0.5) * 2^-23,  key_j = x_j / temperature - ln(-ln u_j)
+ * in fp32;  out_idx [rows] = the kept column with the largest key, ties to the smaller column.  Optional outputs (NULL to
+ * skip): out_top2_idx / out_top2_key [rows, 2] = winner and runner-up among the kept (-1 / -inf when one is kept), out_kept
+ * [rows] = size of the kept set, out_threshold [rows] = its smallest value.  A row's outputs depend on that row's logits,
+ * position, stream and the scalar arguments only -- not on the other rows, their number, or the run.
+ * LS_ERR_INVALID_ARG: vocab or ld not a multiple of 8, misaligned pointers, temperature <= 0, top_k < 0, top_p outside (0, 1]. */
+int ls_sample_rows(const void* logits, int rows, int vocab, int64_t ld, int dtype, const int64_t* positions, const int32_t* streams,
+                   uint64_t seed, float temperature, int top_k, float top_p, int64_t* out_idx, int64_t* out_top2_idx,
+                   float* out_top2_key, int32_t* out_kept, float* out_threshold, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 /* The same two operators with the lm_head SHARDED BY VOCABULARY over the ranks of a node (no counterpart in the reference, which
  * replicates: llama_glide.py:474).  A "record" is what stage 1 produces per (8192-logit chunk, row): the chunk's max, its sum of
  * exp(x - max) and its k largest logits with their GLOBAL columns -- rows * (2 + 2k) floats per chunk slot, chunk-major.

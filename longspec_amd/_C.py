@@ -89,6 +89,9 @@ SYMBOLS = {
     "ls_logprob_topk": (C.c_int, [_P, _I, _I, _L, _I, _P, _I, _P, _P, _P, C.c_size_t, _P]),
     "ls_logprob_topk_store": (C.c_int, [_P, _I, _I, _L, _I, _P, _I, _P, _P, _P, _L, _P, C.c_size_t, _P]),
     "ls_argmax_rows": (C.c_int, [_P, _I, _I, _L, _I, _P, _P, C.c_size_t, _P]),
+    "ls_sample_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "ls_sample_rows": (C.c_int, [_P, _I, _I, _L, _I, _P, _P, C.c_uint64, C.c_float, _I, C.c_float, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                 _P]),
     "ls_topk_chunk": (C.c_int, []),
     "ls_topk_stage1": (C.c_int, [_P, _I, _I, _L, _I, _I, _I, _I, _P, _P]),
     "ls_topk_stage2": (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),

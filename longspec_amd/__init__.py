@@ -5,3 +5,5 @@ from PyTorch-ROCm through the reference's own Python API (`LlamaGlide`,
 `tree_spec_generate`, ...).  See DESIGN.md.
 """
 __version__ = "0.1.0"
+
+from .sampling import Sampling  # noqa: E402,F401

@@ -1,0 +1,390 @@
+// sample.hip -- one draw per row from the tempered, top-k / top-p filtered distribution of the lm_head logits
+// (gfx950 / CDNA4).  No counterpart in the reference: its temperature > 0 paths stay in tree.hip / ops.py as they are.
+//
+// A row's draw is the Gumbel-max of its kept logits, with noise keyed by (seed, stream, position, column) through
+// Philox4x32-10: key_j = x_j / T - ln(-ln u_j), the result is the kept column with the largest key (ties to the smaller
+// column).  Nothing of a row's result depends on the other rows, the row count, the grid or the run: every cross-workgroup
+// quantity is an integer sum (order-free) or a maximum of unique 64-bit keys.
+//
+// The kept set is a threshold set {x_j >= t}.  t comes from a weighted rank selection on the ordered 16-bit pattern of the
+// logits, two 256-bin radix levels, run once per filter:
+//   top-k   weight 1 per logit, target min(k, finite logits): t_k = the k-th largest value (ties all kept);
+//   top-p   weight F(x) = floor(2^40 * exp((x - x_max) / T)) (double precision exp, unsigned 64-bit fixed point) per logit
+//           >= t_k, target ceil(p * sum F): t_p = the largest value v with sum_{x >= v} F >= target.
+// Integer weights make the sum over the tokens of a value EQUAL n(v) * F(v), and the coarse level consistent with the fine
+// one, whatever the order of the additions.  A -inf logit carries no weight and is never kept while the row has a finite one.
+//
+//   sample_hist_kernel    grid (chunks of 8192 logits, rows): 256-bin weight histogram of the chunk at one radix level
+//                         (LDS integer atomics), chunk maximum
+//   sample_select_kernel  grid (rows): bin sums over the chunks, the bin that holds the target, the residual target
+//   sample_key_kernel     grid (chunks, rows): Philox + Gumbel keys of the kept logits, the chunk's two best, kept count,
+//                         smallest kept value
+//   sample_merge_kernel   one thread per row: the row's two best over its chunks, outputs
+// Filters off: the last two launches only.  top-k: + 4.  top-p: + 6 (the first pair finds x_max).
+#include "ls_common.h"
+
+namespace {
+
+constexpr int SM_THREADS = 256;
+constexpr int SM_CHUNK = 8192;          // logits per workgroup: 32 per thread
+constexpr int SM_REC_WORDS = 8;         // candidate record of (row, chunk), 32-bit words: best (2), second (2), finite kept, -inf kept, min kept, pad
+
+struct RowState {
+    unsigned lower;                     // ordered 16-bit key: logits below it take no part (0 = all)
+    unsigned bin;                       // level 0 result: the high byte that holds the target
+    unsigned long long target;          // what is left of the target inside `bin`
+    float m;                            // row maximum
+    unsigned pad[3];
+};
+
+__device__ __forceinline__ unsigned order_key(unsigned bits16) {       // as topk.hip: -0.0 and +0.0 share 0x8000
+    return (bits16 & 0x8000u) ? 0x8000u - (bits16 & 0x7fffu) : (bits16 | 0x8000u);
+}
+__device__ __forceinline__ unsigned order_key32(float f) {
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key32_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+struct Philox {
+    unsigned w[4];
+};
+__device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return Philox{{c0, c1, c2, c3}};
+}
+
+// the 32 logits of a thread: element e = j*8 + i sits at column col0[j] + i
+template <typename E>
+struct Chunk {
+    uint32_t raw[16];
+    int col0[4];
+    int V;
+    __device__ __forceinline__ void load(const typename E::T* src, int base, int V_, int tid) {
+        V = V_;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = base + (j * SM_THREADS + tid) * 8;
+            col0[j] = c;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (c < V) v = *reinterpret_cast<const uint4*>(src + c);                       // V % 8 == 0: all-in or all-out
+            raw[j * 4 + 0] = v.x; raw[j * 4 + 1] = v.y; raw[j * 4 + 2] = v.z; raw[j * 4 + 3] = v.w;
+        }
+    }
+    __device__ __forceinline__ unsigned bits(int e) const { return (raw[e >> 1] >> ((e & 1) * 16)) & 0xffffu; }
+    __device__ __forceinline__ float val(int e) const {
+        const unsigned short h = (unsigned short)bits(e);
+        return E::to_f32(__builtin_bit_cast(typename E::T, h));
+    }
+    __device__ __forceinline__ bool valid(int e) const { return col0[e >> 3] < V; }
+};
+
+// mode 0: weight 1; mode 1: weight F(x).  level 0: bin = high byte; level 1: low byte of the logits whose high byte is st.bin
+template <typename E>
+__global__ __launch_bounds__(SM_THREADS) void sample_hist_kernel(const typename E::T* __restrict__ logits, long ld, int V, int level,
+                                                                 int mode, float T, const RowState* __restrict__ state,
+                                                                 unsigned long long* __restrict__ hist, float* __restrict__ chunk_max) {
+    __shared__ unsigned long long s_hist[256];
+    __shared__ float s_red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int chunk = blockIdx.x, row = blockIdx.y, nchunks = gridDim.x;
+    Chunk<E> ck;
+    ck.load(logits + (long)row * ld, chunk * SM_CHUNK, V, tid);
+    s_hist[tid] = 0ull;
+    const bool first = level == 0 && mode == 0;          // the launch that nothing precedes: the state is not read
+    const unsigned lower = first ? 0u : state[row].lower;
+    const unsigned prefix = level ? state[row].bin : 0u;
+    const double m = mode ? (double)state[row].m : 0.0;
+    if (first) {
+        float cm = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 32; ++e)
+            if (ck.valid(e)) cm = fmaxf(cm, ck.val(e));
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) cm = fmaxf(cm, __shfl_xor(cm, off));
+        if (lane == 0) s_red[wave] = cm;
+    }
+    __syncthreads();
+    if (first && tid == 0) chunk_max[(long)row * nchunks + chunk] = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+#pragma unroll
+    for (int e = 0; e < 32; ++e) {
+        const unsigned key = order_key(ck.bits(e));
+        const float x = ck.val(e);
+        if (!ck.valid(e) || x == -INFINITY || key < lower) continue;
+        if (level && (key >> 8) != prefix) continue;
+        unsigned long long w = 1ull;
+        if (mode) w = (unsigned long long)(exp(((double)x - m) / (double)T) * 1099511627776.0);     // 2^40; x <= m
+        atomicAdd(&s_hist[level ? (key & 255u) : (key >> 8)], w);
+    }
+    __syncthreads();
+    hist[((long)row * nchunks + chunk) * 256 + tid] = s_hist[tid];
+}
+
+__device__ __forceinline__ unsigned long long shfl_down64(unsigned long long v, int off) {
+    const unsigned lo = __shfl_down((unsigned)v, off), hi = __shfl_down((unsigned)(v >> 32), off);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// One workgroup per row, one thread per bin.  Level 0 fixes the target and the high byte; level 1 the threshold key, which
+// becomes the row's `lower`.  A row without weight (all -inf) keeps lower = 0: everything is kept.
+__global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(int level, int mode, int k, float p, int nchunks,
+                                                                   RowState* __restrict__ state,
+                                                                   const unsigned long long* __restrict__ hist,
+                                                                   const float* __restrict__ chunk_max) {
+    __shared__ unsigned long long s_wave[4];
+    __shared__ float s_cm[4];
+    const int tid = threadIdx.x, row = blockIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long w = 0ull;
+#pragma unroll 8
+    for (int c = 0; c < nchunks; ++c) w += hist[((long)row * nchunks + c) * 256 + tid];
+    float cm = -INFINITY;                                // the row maximum, from the chunk maxima (first launch only)
+    if (level == 0 && mode == 0)
+        for (int c = tid; c < nchunks; c += SM_THREADS) cm = fmaxf(cm, chunk_max[(long)row * nchunks + c]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) cm = fmaxf(cm, __shfl_xor(cm, off));
+    if (lane == 0) s_cm[wave] = cm;
+    // weight of this bin and the bins beyond it: suffix sums inside the wave, then the totals of the waves above
+    unsigned long long incl = w;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long o = shfl_down64(incl, off);
+        if (lane + off < 64) incl += o;
+    }
+    if (lane == 0) s_wave[wave] = incl;
+    __syncthreads();
+    for (int q = wave + 1; q < 4; ++q) incl += s_wave[q];
+    const unsigned long long above = incl - w;
+    const unsigned long long total = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+    unsigned long long target;
+    if (level) {
+        target = state[row].target;
+    } else if (mode == 0) {
+        target = (unsigned long long)k < total ? (unsigned long long)k : total;
+    } else {
+        target = (unsigned long long)ceil((double)p * (double)total);
+        if (target < 1ull) target = 1ull;
+        if (target > total) target = total;
+    }
+    if (level == 0 && mode == 0 && tid == 0) {
+        state[row].m = fmaxf(fmaxf(s_cm[0], s_cm[1]), fmaxf(s_cm[2], s_cm[3]));
+        state[row].lower = 0u;
+    }
+    if (total == 0ull) {
+        if (tid == 0 && level == 0) { state[row].bin = 0u; state[row].target = 0ull; }
+        return;
+    }
+    if (incl >= target && above < target) {              // exactly one bin
+        if (level == 0) {
+            state[row].bin = (unsigned)tid;
+            state[row].target = target - above;
+        } else {
+            state[row].lower = (state[row].bin << 8) | (unsigned)tid;
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned long long shfl_xor64(unsigned long long v, int off) {
+    const unsigned lo = __shfl_xor((unsigned)v, off), hi = __shfl_xor((unsigned)(v >> 32), off);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// two best of the union of two (best, second) pairs; keys are unique or 0 (= none)
+__device__ __forceinline__ void top2_merge(unsigned long long& a1, unsigned long long& a2, unsigned long long b1, unsigned long long b2) {
+    const unsigned long long hi = a1 > b1 ? a1 : b1, lo = a1 > b1 ? b1 : a1;
+    const unsigned long long s = a2 > b2 ? a2 : b2;
+    a1 = hi;
+    a2 = lo > s ? lo : s;
+}
+
+template <typename E>
+__global__ __launch_bounds__(SM_THREADS) void sample_key_kernel(const typename E::T* __restrict__ logits, long ld, int V,
+                                                                const int64_t* __restrict__ positions,
+                                                                const int32_t* __restrict__ streams, unsigned seed_lo,
+                                                                unsigned seed_hi, float T, int filtered,
+                                                                const RowState* __restrict__ state, unsigned* __restrict__ cand) {
+    __shared__ unsigned long long s_b[8];
+    __shared__ int s_n[8];
+    __shared__ float s_min[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int chunk = blockIdx.x, row = blockIdx.y, nchunks = gridDim.x;
+    Chunk<E> ck;
+    ck.load(logits + (long)row * ld, chunk * SM_CHUNK, V, tid);
+    const unsigned lower = filtered ? state[row].lower : 0u;
+    const unsigned long long pos = (unsigned long long)positions[row];
+    const unsigned strm = streams ? (unsigned)streams[row] : 0u;
+    unsigned long long b1 = 0ull, b2 = 0ull;             // (ordered fp32 key << 32) | ~column
+    int n_fin = 0, n_inf = 0;
+    float vmin = INFINITY;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {                        // 4 consecutive columns share one Philox block
+        const int c = ck.col0[q >> 1] + (q & 1) * 4;
+        if (c >= V) continue;
+        const Philox r = philox4x32_10((unsigned)c >> 2, (unsigned)pos, (unsigned)(pos >> 32), strm, seed_lo, seed_hi);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = q * 4 + i;
+            if (order_key(ck.bits(e)) < lower) continue;
+            const float x = ck.val(e);
+            const float u = ((float)(r.w[i] >> 9) + 0.5f) * 1.1920928955078125e-07f;       // 2^-23: exact, in (0, 1)
+            const float key = x / T - logf(-logf(u));
+            const unsigned long long pk = ((unsigned long long)order_key32(key) << 32) | (0xffffffffu - (unsigned)(c + i));
+            if (pk > b1) { b2 = b1; b1 = pk; }
+            else if (pk > b2) b2 = pk;
+            if (x == -INFINITY) ++n_inf;
+            else { ++n_fin; vmin = fminf(vmin, x); }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        top2_merge(b1, b2, shfl_xor64(b1, off), shfl_xor64(b2, off));
+        n_fin += __shfl_xor(n_fin, off);
+        n_inf += __shfl_xor(n_inf, off);
+        vmin = fminf(vmin, __shfl_xor(vmin, off));
+    }
+    if (lane == 0) {
+        s_b[wave * 2] = b1; s_b[wave * 2 + 1] = b2;
+        s_n[wave * 2] = n_fin; s_n[wave * 2 + 1] = n_inf;
+        s_min[wave] = vmin;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w) {
+            top2_merge(b1, b2, s_b[w * 2], s_b[w * 2 + 1]);
+            n_fin += s_n[w * 2];
+            n_inf += s_n[w * 2 + 1];
+            vmin = fminf(vmin, s_min[w]);
+        }
+        unsigned* rec = cand + ((long)row * nchunks + chunk) * SM_REC_WORDS;
+        rec[0] = (unsigned)b1; rec[1] = (unsigned)(b1 >> 32);
+        rec[2] = (unsigned)b2; rec[3] = (unsigned)(b2 >> 32);
+        rec[4] = (unsigned)n_fin; rec[5] = (unsigned)n_inf;
+        rec[6] = __float_as_uint(vmin); rec[7] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(SM_THREADS) void sample_merge_kernel(const unsigned* __restrict__ cand, int rows, int nchunks,
+                                                                  int64_t* __restrict__ out_idx, int64_t* __restrict__ top2_idx,
+                                                                  float* __restrict__ top2_key, int32_t* __restrict__ out_kept,
+                                                                  float* __restrict__ out_thr) {
+    const int row = blockIdx.x * SM_THREADS + threadIdx.x;
+    if (row >= rows) return;
+    unsigned long long b1 = 0ull, b2 = 0ull;
+    long n_fin = 0, n_inf = 0;
+    float vmin = INFINITY;
+    for (int c = 0; c < nchunks; ++c) {
+        const unsigned* rec = cand + ((long)row * nchunks + c) * SM_REC_WORDS;
+        top2_merge(b1, b2, ((unsigned long long)rec[1] << 32) | rec[0], ((unsigned long long)rec[3] << 32) | rec[2]);
+        n_fin += rec[4];
+        n_inf += rec[5];
+        vmin = fminf(vmin, __uint_as_float(rec[6]));
+    }
+    // -inf logits (key -inf) only count while the row has no finite logit at all
+    const long kept = n_fin > 0 ? n_fin : n_inf;
+    if (kept < 2) b2 = 0ull;
+    out_idx[row] = (int64_t)(0xffffffffu - (unsigned)b1);
+    if (top2_idx) {
+        top2_idx[row * 2] = (int64_t)(0xffffffffu - (unsigned)b1);
+        top2_idx[row * 2 + 1] = b2 ? (int64_t)(0xffffffffu - (unsigned)b2) : -1;
+    }
+    if (top2_key) {
+        top2_key[row * 2] = key32_value((unsigned)(b1 >> 32));
+        top2_key[row * 2 + 1] = b2 ? key32_value((unsigned)(b2 >> 32)) : -INFINITY;
+    }
+    if (out_kept) out_kept[row] = (int32_t)kept;
+    if (out_thr) out_thr[row] = n_fin > 0 ? vmin : -INFINITY;
+}
+
+struct SampleWs {
+    size_t state, cmax, hist, cand, total;
+};
+SampleWs sample_ws(int rows, int vocab) {
+    const size_t nchunks = ((size_t)vocab + SM_CHUNK - 1) / SM_CHUNK;
+    SampleWs w;
+    w.state = 0;
+    w.hist = (size_t)rows * sizeof(RowState);
+    w.cand = w.hist + (size_t)rows * nchunks * 256 * sizeof(unsigned long long);
+    w.cmax = w.cand + (size_t)rows * nchunks * SM_REC_WORDS * sizeof(unsigned);
+    w.total = w.cmax + ((size_t)rows * nchunks * sizeof(float) + 15) / 16 * 16;
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ls_sample_workspace_bytes(int rows, int vocab) {
+    if (rows < 1 || vocab < 8) return 0;
+    return sample_ws(rows, vocab).total;
+}
+
+int ls_sample_rows(const void* logits, int rows, int vocab, int64_t ld, int dtype, const int64_t* positions, const int32_t* streams,
+                   uint64_t seed, float temperature, int top_k, float top_p, int64_t* out_idx, int64_t* out_top2_idx,
+                   float* out_top2_key, int32_t* out_kept, float* out_threshold, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+    if (!logits || !positions || !out_idx || !workspace) LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows: null pointer");
+    if (dtype != LS_F16 && dtype != LS_BF16) LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows: dtype");
+    if (rows < 1 || rows > 65535 || vocab < 8 || vocab > (1 << 24) || vocab % 8 != 0 || ld < vocab || ld % 8 != 0)
+        LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows: rows=%d vocab=%d ld=%ld (vocab and ld must be multiples of 8, rows <= 65535, "
+                "vocab <= 2^24)", rows, vocab, (long)ld);
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f) || !(top_p <= 1.f))
+        LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows: temperature=%g (> 0), top_k=%d (>= 0), top_p=%g (0 < p <= 1)", (double)temperature,
+                top_k, (double)top_p);
+    if (reinterpret_cast<uintptr_t>(logits) % 16 != 0 || reinterpret_cast<uintptr_t>(workspace) % 16 != 0)
+        LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows: logits and workspace must be 16-byte aligned");
+    const SampleWs w = sample_ws(rows, vocab);
+    if (workspace_bytes < w.total) LS_FAIL(LS_ERR_WORKSPACE, "ls_sample_rows: workspace too small");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* base = static_cast<char*>(workspace);
+    RowState* state = reinterpret_cast<RowState*>(base + w.state);
+    unsigned long long* hist = reinterpret_cast<unsigned long long*>(base + w.hist);
+    unsigned* cand = reinterpret_cast<unsigned*>(base + w.cand);
+    float* cmax = reinterpret_cast<float*>(base + w.cmax);
+    const int nchunks = (vocab + SM_CHUNK - 1) / SM_CHUNK;
+    const dim3 grid(nchunks, rows), block(SM_THREADS);
+    const bool use_k = top_k > 0 && top_k < vocab, use_p = top_p < 1.f;
+    auto hist_pass = [&](int level, int mode) -> int {
+        if (dtype == LS_F16)
+            hipLaunchKernelGGL(sample_hist_kernel<ElemF16>, grid, block, 0, s, static_cast<const _Float16*>(logits), (long)ld, vocab,
+                               level, mode, temperature, state, hist, cmax);
+        else
+            hipLaunchKernelGGL(sample_hist_kernel<ElemBF16>, grid, block, 0, s, static_cast<const __bf16*>(logits), (long)ld, vocab,
+                               level, mode, temperature, state, hist, cmax);
+        LS_CHECK_LAUNCH("sample_hist_kernel");
+        hipLaunchKernelGGL(sample_select_kernel, dim3(rows), block, 0, s, level, mode, use_k ? top_k : vocab, top_p, nchunks, state,
+                           hist, cmax);
+        LS_CHECK_LAUNCH("sample_select_kernel");
+        return LS_OK;
+    };
+    int rc;
+    if (use_k || use_p) {
+        if ((rc = hist_pass(0, 0))) return rc;           // also the row maximum and lower = 0
+        if (use_k && (rc = hist_pass(1, 0))) return rc;
+        if (use_p) {
+            if ((rc = hist_pass(0, 1))) return rc;
+            if ((rc = hist_pass(1, 1))) return rc;
+        }
+    }
+    const int filtered = (use_k || use_p) ? 1 : 0;
+    if (dtype == LS_F16)
+        hipLaunchKernelGGL(sample_key_kernel<ElemF16>, grid, block, 0, s, static_cast<const _Float16*>(logits), (long)ld, vocab,
+                           positions, streams, (unsigned)seed, (unsigned)(seed >> 32), temperature, filtered, state, cand);
+    else
+        hipLaunchKernelGGL(sample_key_kernel<ElemBF16>, grid, block, 0, s, static_cast<const __bf16*>(logits), (long)ld, vocab,
+                           positions, streams, (unsigned)seed, (unsigned)(seed >> 32), temperature, filtered, state, cand);
+    LS_CHECK_LAUNCH("sample_key_kernel");
+    hipLaunchKernelGGL(sample_merge_kernel, dim3((rows + SM_THREADS - 1) / SM_THREADS), block, 0, s, cand, rows, nchunks, out_idx,
+                       out_top2_idx, out_top2_key, out_kept, out_threshold);
+    LS_CHECK_LAUNCH("sample_merge_kernel");
+    return LS_OK;
+}
+
+}  // extern "C"

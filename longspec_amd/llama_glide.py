@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from .graphs import GraphReplayer
+from .sampling import resolve as _resolve_sampling
 from .llama import (DecodeLinear, LlamaForCausalLM, LlamaMLP, LlamaRMSNorm, chunked_causal_prefill,
                     project_qkv, _default_ops)
 
@@ -340,6 +341,25 @@ class LlamaGlide(LlamaForCausalLM):
             position_ids = torch.arange(ids.size(1), device=ids.device)[None, :] + pos_base[:, None] + pos_add
         return hidden_states, None, self.model.rotary_emb(hidden_states, position_ids)
 
+    def _target_tokens(self, logits, sampling, positions, streams=None):
+        """The target's token for every row of ``logits`` [bsz, (rows,) V]: the arg-max, or with ``sampling`` one draw per row
+        (``ops.sample_rows``) keyed by ``positions`` -- the positions RoPE saw for those rows -- and the batch row."""
+        if sampling is None:
+            return self.ops.argmax_rows(logits)
+        bsz = logits.size(0)
+        if streams is None and bsz > 1:
+            streams = torch.arange(bsz, device=logits.device, dtype=torch.int32)
+        if streams is not None and logits.dim() == 3:
+            streams = streams.view(bsz, 1).expand(bsz, logits.size(1))
+        return self.ops.sample_rows(logits, positions, sampling, streams=streams)
+
+    def _first_token(self, logits, sampling, input_len):
+        """The prefill's token from ``logits`` [bsz, V] of prompt row ``input_len - 1``."""
+        if sampling is None:
+            return logits.argmax(dim=-1)
+        positions = input_len.to(device=logits.device, dtype=torch.int64).view(-1) - 1
+        return self._target_tokens(logits, sampling, positions)
+
     def _stop_id(self, eos_id, loop: str):
         """Token whose appearance ends a loop.  The Llama twin tests ``self.config.eos_token_id`` in all
         three loops (llama_glide.py:578,767,1120) and ignores the ``eos_id`` argument for that."""
@@ -362,8 +382,11 @@ class LlamaGlide(LlamaForCausalLM):
         self.glide.cross_attn.shard = None
 
     @torch.inference_mode()
-    def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645):       # :552-585
+    def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645, sampling=None):       # :552-585
+        """``sampling`` (``longspec_amd.Sampling``): every token is drawn from the target's filtered distribution instead of
+        taken as its arg-max -- the denominator of a sampled speculative run, and with the same seed the same text."""
         assert input_ids is not None, "please give the input"
+        sampling = _resolve_sampling(sampling, None, use_env=True)
         self._clear_shard()
         bsz = input_ids.size(0)
         output_ids = input_ids.new_zeros((bsz, max_gen_len))
@@ -374,7 +397,7 @@ class LlamaGlide(LlamaForCausalLM):
         hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
         input_len = prompt_length
         rows = torch.arange(bsz, device=input_ids.device)
-        output_ids[:, 0] = self.lm_head(hidden_states[rows, input_len - 1, :]).argmax(dim=-1)
+        output_ids[:, 0] = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), sampling, input_len)
         cache_lens += input_len.int()
         num = 0
         eos = self._stop_id(eos_id, "vanilla")
@@ -385,7 +408,7 @@ class LlamaGlide(LlamaForCausalLM):
         if on_gpu:
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record()
-        vs = self.begin_vanilla_decode(output_ids, cache_lens, input_len.int(), P)
+        vs = self.begin_vanilla_decode(output_ids, cache_lens, input_len.int(), P, sampling=sampling)
         for step in range(1, max_gen_len):
             self.vanilla_step(vs)
             num += bsz
@@ -409,12 +432,15 @@ class LlamaGlide(LlamaForCausalLM):
         return output_ids, num, elapsed_time
 
     # ------------------------------------------------------------------------------------------
-    def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int):
+    def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int, sampling=None):
         """State of the vanilla loop (``llama_glide.py:566-583``): ``output_ids`` [bsz, max_gen] with the first
-        token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32."""
+        token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32.  ``sampling``:
+        draw instead of arg-max (None: the process-wide default LONGSPEC_SAMPLING, else greedy)."""
         dev = output_ids.device
+        sampling = _resolve_sampling(sampling, None, use_env=True)
         vs = _DecodeState(output_ids=output_ids, cache_lens=cache_lens, input_len=input_len, P=prompt_bound, step=0,
-                          rows=torch.arange(output_ids.size(0), device=dev))
+                          rows=torch.arange(output_ids.size(0), device=dev), sampling=sampling)
+        vs.streams = torch.arange(output_ids.size(0), device=dev, dtype=torch.int32) if sampling is not None else None
         vs.use_graphs = bool(dev.type == "cuda" and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
         P = prompt_bound                                   # (the replayer holds no reference to the state that holds it)
         vs.replayer = GraphReplayer(self, lambda bound: (P + bound, P + bound), output_ids.size(1), "vanilla step")
@@ -425,7 +451,8 @@ class LlamaGlide(LlamaForCausalLM):
         out, cl, il, rows = vs.output_ids, vs.cache_lens, vs.input_len, vs.rows
         cur = out[rows, (cl - il).long()].view(out.size(0), -1)
         hidden_states = self.model.forward(cur, cache_lens=cl, exec_type="decoding").last_hidden_state
-        llm_output = self.ops.argmax_rows(self.lm_head(hidden_states[:, -1, :]))
+        # (sampling: the row was rotated to position cl, the length before this step's increment)
+        llm_output = self._target_tokens(self.lm_head(hidden_states[:, -1, :]), vs.sampling, cl, vs.streams)
         cl += 1
         out[rows, (cl - il).long()] = llm_output.view(-1)
 
@@ -452,15 +479,19 @@ class LlamaGlide(LlamaForCausalLM):
 
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
-    def spec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0):   # :621-774
-        return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="glide")
+    def spec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
+                      sampling=None):                                                                              # :621-774
+        return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="glide",
+                                    sampling=sampling)
 
     @torch.inference_mode()
-    def magicdec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0):  # :776-913
+    def magicdec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
+                          sampling=None):                                                                          # :776-913
         """The MagicDec baseline of the reference's harness (``--method magicdec``): chain speculation where the
         drafter is the TARGET itself attending to a StreamingLLM cache (32 sink rows + the last 1024 prompt rows +
         what it generates), verified exactly like ``spec_generate``.  Same return tuple."""
-        return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="magicdec")
+        return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="magicdec",
+                                    sampling=sampling)
 
     @torch.inference_mode()
     def vanilla_torch_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645):                      # :587-619
@@ -470,8 +501,9 @@ class LlamaGlide(LlamaForCausalLM):
         time flash-attn against eager attention)."""
         return self.vanilla_generate(input_ids, prompt_length, max_gen_len=max_gen_len, eos_id=eos_id)
 
-    def _chain_generate(self, input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter):
+    def _chain_generate(self, input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter, sampling=None):
         assert input_ids is not None, "please give the input"
+        sampling = _resolve_sampling(sampling, temperature, use_env=True)
         magic = drafter == "magicdec"       # (temperature > 0: the same rejection block in both loops, :715-736 = :854-875)
         self._clear_shard()
         bsz = input_ids.size(0)
@@ -493,8 +525,8 @@ class LlamaGlide(LlamaForCausalLM):
             position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=cache_lens.clone(), llm_kv_len=cache_lens.clone(), exec_type="prefill")
-        st = self.begin_chain_decode(logits.argmax(dim=-1), cache_lens, input_len, P, gamma, max_gen_len, eos_id, temperature,
-                                     drafter, first_logits=logits)
+        st = self.begin_chain_decode(self._first_token(logits, sampling, input_len), cache_lens, input_len, P, gamma, max_gen_len,
+                                     eos_id, temperature, drafter, first_logits=logits, sampling=sampling)
         _sync(input_ids)
         start_time = time.time()
         for out_index in range(1, max_gen_len):
@@ -505,17 +537,21 @@ class LlamaGlide(LlamaForCausalLM):
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
     def begin_chain_decode(self, first_token, cache_lens, input_len, prompt_bound: int, gamma=4, max_gen_len=64, eos_id=151645,
-                           temperature=0.0, drafter="glide", first_logits=None):
+                           temperature=0.0, drafter="glide", first_logits=None, sampling=None):
         """State of the chain-speculation loop right after the prefills (``llama_glide.py:641-668``): ``first_token`` [bsz]
         = the target's first generated token, ``cache_lens`` [bsz] int32 = valid rows of every cache (the draft's included),
         ``input_len`` [bsz] = prompt length, ``prompt_bound`` = host-side bound of it.  Also the entry point of benchmarks
-        that time ``chain_round`` on synthetic KV (bench.py --method seq)."""
+        that time ``chain_round`` on synthetic KV (bench.py --method seq).  ``sampling``: the verification pass draws its
+        tokens instead of taking arg-maxes (None at temperature 0: the process-wide default LONGSPEC_SAMPLING, else greedy);
+        the drafter stays greedy."""
         bsz = first_token.size(0)
         dev = first_token.device
+        sampling = _resolve_sampling(sampling, temperature, use_env=True)
         if drafter != "magicdec":
             self._head_of_draft_passes()                # the draft passes' head and its pack exist before the first round
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
-                             max_gen_len=max_gen_len, count=0, num=0, emitted=1, double_flag=False)
+                             max_gen_len=max_gen_len, count=0, num=0, emitted=1, double_flag=False, sampling=sampling)
+        st.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if sampling is not None else None
         st.output_ids = first_token.new_zeros((bsz, max_gen_len + gamma))
         st.spec_mask = first_token.new_zeros((bsz, max_gen_len + gamma))
         st.output_ids[:, 0] = first_token
@@ -588,7 +624,9 @@ class LlamaGlide(LlamaForCausalLM):
                     spec_logits[:, spec_steps + 1, :] = current_logp
         hidden_states = self.model.forward(spec_buffer, cache_lens=cache_lens, exec_type="decoding").last_hidden_state
         llm_verify_logits = self.lm_head(hidden_states[:, -gamma - 1:, :])
-        llm_verify_output = self.ops.argmax_rows(llm_verify_logits)
+        # (sampling: verification row i was rotated to position cache_lens + i, models' forward :571-577)
+        llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
+                                                cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
         accept = None
         if st.temperature > 0:                               # :715-736
             llm_verify_output, accept = self.ops.chain_accept_stochastic(spec_logits, llm_verify_logits, spec_buffer,
@@ -609,11 +647,15 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def tree_spec_generate(self, input_ids, prompt_length, tree_shape: Optional[List[int]] = None, max_gen_len=64,
-                           eos_id=151645, temperature=0.0, shard=None):                       # :915-1126
+                           eos_id=151645, temperature=0.0, shard=None, sampling=None):        # :915-1126
         """``shard`` (``dist.KVShard``, every rank of the group calls with the same arguments): the prompt is prefilled
         and its KV kept sequence-sharded over the ranks (``_sharded_prefill``); decoding then runs replicated with one
-        exchange per attention call.  Returns the same values on every rank."""
+        exchange per attention call.  Returns the same values on every rank.  ``sampling``: the verification pass draws
+        one token per row and the greedy acceptance runs on the draws (not with a vocabulary-parallel shard)."""
         assert input_ids is not None, "please give the input"
+        sampling = _resolve_sampling(sampling, temperature, use_env=True)
+        if sampling is not None and shard is not None and shard.vocab_parallel:
+            raise ValueError("sampling= is not available with a vocabulary-parallel shard")
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
         dev = input_ids.device
@@ -632,18 +674,18 @@ class LlamaGlide(LlamaForCausalLM):
                 # a mailbox slot holds the record of the widest pass: 128 rows x heads x (128 + 1) floats
                 heads = max(self.config.num_attention_heads, self.glide.config.num_attention_heads)
                 shard.enable_peer_exchange(bsz * 128 * heads * 129, dev)
-            first = self._sharded_prefill(input_ids, input_len, position_ids, shard)
+            first = self._sharded_prefill(input_ids, input_len, position_ids, shard, sampling)
         else:
             # prefill LLM (:954-960)
             self._set_hints(P, P)
             hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
-            first = self.lm_head(hidden_states[rows, input_len - 1, ...]).argmax(dim=-1)
+            first = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), sampling, input_len)
             # prefill glide (:968-975)
             hidden_states = self.model.embed_tokens(input_ids)
             position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=lens.clone(), llm_kv_len=lens.clone(), exec_type="prefill")
-        st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature)
+        st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature, sampling=sampling)
         _sync(input_ids)
         start_time = time.time()
         for out_index in range(1, max_gen_len):
@@ -660,7 +702,7 @@ class LlamaGlide(LlamaForCausalLM):
             shard.raise_if_exchange_failed()
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
-    def _sharded_prefill(self, input_ids, input_len, position_ids, shard):
+    def _sharded_prefill(self, input_ids, input_len, position_ids, shard, sampling=None):
         """Sequence-sharded prefill: rank r runs the target model on prompt rows [r*Ls, (r+1)*Ls) only
         (one all-gather of the layer's K/V rows per layer, ``LlamaAttention.sharded_prefill``) and keeps that slice of the
         KV; the tail rank computes the first token and broadcasts it.  The draft layer's cache is filled on every rank
@@ -684,19 +726,25 @@ class LlamaGlide(LlamaForCausalLM):
             shard.prefill_ctx = None
         first = torch.zeros((bsz,), dtype=torch.int64, device=input_ids.device)
         if shard.is_tail:
-            first = self.lm_head(hidden_states[:, hi - lo - 1, :]).argmax(dim=-1)
+            first = self._first_token(self.lm_head(hidden_states[:, hi - lo - 1, :]), sampling, input_len)
         shard.broadcast_from_tail(first)
         hidden_states = self.model.embed_tokens(input_ids)
         self.glide.prefill_cache_only(hidden_states, self.model.rotary_emb(hidden_states, position_ids))
         return first
 
     def begin_tree_decode(self, first_token, cache_lens, prompt_bound: int, tree_shape=None, max_gen_len=64, eos_id=151645,
-                          temperature=0.0):
+                          temperature=0.0, sampling=None):
         """State of the round loop right after the two prefills (``llama_glide.py:927-991``).
         ``first_token`` [bsz] = the target's first generated token, ``cache_lens`` [bsz] int32 = valid
         rows of every KV cache, ``prompt_bound`` = host-side bound of it.  Also the entry point of
-        synthetic-KV benchmarks, which fill the caches themselves instead of prefilling."""
+        synthetic-KV benchmarks, which fill the caches themselves instead of prefilling.  ``sampling``: the round is the
+        temperature-0 round with the arg-max of the verification logits replaced by one draw per row (None at temperature 0:
+        the process-wide default LONGSPEC_SAMPLING, else greedy)."""
         dev = first_token.device
+        sampling = _resolve_sampling(sampling, temperature, use_env=True)
+        sh = self.model.layers[-1].self_attn.shard
+        if sampling is not None and sh is not None and sh.vocab_parallel:
+            raise ValueError("sampling= is not available with a vocabulary-parallel shard")
         bsz = first_token.shape[0]
         cand = [4, 16, 16, 16, 16] if tree_shape is None else list(tree_shape)
         acc_n = [1]
@@ -706,7 +754,7 @@ class LlamaGlide(LlamaForCausalLM):
         gamma = len(cand)
         R = Fn - 1 + gamma + 1               # verification rows: [a accepted | F-1 tree | pads]
         self._head_of_draft_passes()                    # the draft passes' head and its pack exist before the first warm-up round
-        st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz)
+        st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz, sampling=sampling)
         st.output_ids = torch.full((bsz, max_gen_len), self._tree_output_fill(eos_id), dtype=torch.int64, device=dev)  # :937 (G8)
         st.spec_mask = torch.zeros((bsz, max_gen_len), dtype=torch.int64, device=dev)
         st.output_ids[:, 0] = first_token
@@ -909,7 +957,9 @@ class LlamaGlide(LlamaForCausalLM):
         if vsh is not None:
             all_llm_pred = vsh.head_select(self.lm_head, hidden_states, ops, argmax=True).view(bsz, -1)
         else:
-            all_llm_pred = ops.argmax_rows(self.lm_head(hidden_states))
+            # (sampling: rows a-1 .. a+Fn-2 of the pass, at the positions ops.tree_verify_inputs gave RoPE for them)
+            all_llm_pred = self._target_tokens(self.lm_head(hidden_states), st.sampling,
+                                               position_ids[:, a - 1:a + Fn - 1] if st.sampling is not None else None)
         # ---- A: accept / reject tree collapse + last-layer KV row move (:1104-1116); the accepted rows start at
         # cache_lens + a - 1 (:1104), the cache lengths themselves advance in the commit below
         sh = last_attn.shard

@@ -11,6 +11,8 @@ One function per reference seam of the draft-then-verify round:
   lse_merge              N-way form of llama.py:385-387,420 for sequence-sharded prefix KV
   logprob_topk / argmax_rows   beam growth and greedy verification on the lm_head logits  llama_glide.py:1019-1064,1091
                          (logp_out=: the draft's log-prob table of the temperature > 0 rounds, :1025,1074)
+  sample_rows            one draw per row from the target's tempered, top-k / top-p filtered distribution (sampling=;
+                         no counterpart in the reference)
   tree_commit / tree_commit_stochastic   end of a round at temperature 0 / > 0  llama_glide.py:1093-1121
   linear / linear_multi / mlp_gate_up   the projections of a decode pass (M <= 80 token rows):
                          q/k/v/o_proj llama.py:361-363,390, LlamaMLP (qwen2.py:218-230), lm_head llama_glide.py:1091
@@ -100,7 +102,7 @@ _gemm_ws = _ZeroedWorkspace()
 
 def workspace_tensors():
     """The scratch buffers currently handed out (a captured HIP graph keeps them alive: it holds their addresses)."""
-    return list(_ws._buf.values()) + list(_gemm_ws._buf.values())
+    return list(_ws._buf.values()) + list(_gemm_ws._buf.values()) + list(_sample_ws._buf.values())
 
 
 _linear_need = {}            # (shape key) -> workspace bytes of the launch plan
@@ -350,6 +352,51 @@ def argmax_rows(logits: torch.Tensor) -> torch.Tensor:
     ws = _ws.get(logits.device, max(need, 1))
     _C.check(lib.ls_argmax_rows(x.data_ptr(), x.shape[0], V, x.stride(0), _dtype(x), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                 _stream()), "ls_argmax_rows")
+    return out.view(shape)
+
+
+_sample_ws = _Workspace()    # its own buffer: a captured round holds its address, and other operators' growth must not move it
+
+
+def sample_rows(logits: torch.Tensor, positions: torch.Tensor, sampling, streams: Optional[torch.Tensor] = None,
+                return_top2: bool = False):
+    """One draw per row of lm_head outputs [..., V] from soft-max(x / T) under ``sampling``'s top-k / top-p
+    (``ls_sample_rows``): int64 [...].  ``positions`` [...] int64 = absolute position of the token each row PREDICTS FROM
+    (the position fed to RoPE for that row), ``streams`` [...] int32 = its batch row (None: 0) -- with the seed they key the
+    noise, so a position draws the same noise in every loop.  ``return_top2``: also (top2_idx [..., 2], top2_key [..., 2],
+    kept [...] int32, threshold [...] fp32)."""
+    _dev(logits, positions, streams)
+    shape = logits.shape[:-1]
+    V = logits.shape[-1]
+    x = logits.reshape(-1, V)
+    if x.stride(-1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    n = x.shape[0]
+    pos = positions.reshape(-1).to(torch.int64).contiguous()
+    if pos.numel() != n:
+        raise ValueError(f"sample_rows: {n} rows of logits, {pos.numel()} positions")
+    strm = None
+    if streams is not None:
+        strm = streams.reshape(-1).to(torch.int32).contiguous()
+        if strm.numel() != n:
+            raise ValueError(f"sample_rows: {n} rows of logits, {strm.numel()} streams")
+    dev = logits.device
+    out = torch.empty((n,), dtype=torch.int64, device=dev)
+    t2i = t2k = kept = thr = None
+    if return_top2:
+        t2i = torch.empty((n, 2), dtype=torch.int64, device=dev)
+        t2k = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        kept = torch.empty((n,), dtype=torch.int32, device=dev)
+        thr = torch.empty((n,), dtype=torch.float32, device=dev)
+    lib = _C.load()
+    need = lib.ls_sample_workspace_bytes(n, V)
+    ws = _sample_ws.get(dev, max(need, 1))
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _C.check(lib.ls_sample_rows(x.data_ptr(), n, V, x.stride(0), _dtype(x), pos.data_ptr(), ptr(strm), sampling.seed,
+                                sampling.temperature, sampling.top_k, sampling.top_p, out.data_ptr(), ptr(t2i), ptr(t2k), ptr(kept),
+                                ptr(thr), ws.data_ptr(), ws.numel(), _stream()), "ls_sample_rows")
+    if return_top2:
+        return out.view(shape), t2i.view(*shape, 2), t2k.view(*shape, 2), kept.view(shape), thr.view(shape)
     return out.view(shape)
 
 
