@@ -359,7 +359,35 @@ int ls_sample_rows(const void* logits, int rows, int vocab, int64_t ld, int dtyp
                    float* out_top2_key, int32_t* out_kept, float* out_threshold, void* workspace, size_t workspace_bytes,
                    void* stream);
 
-/* The same two operators with the lm_head SHARDED BY VOCABULARY over the ranks of a node (no counterpart in the reference, which
+/* Token penalties and a logit bias on TARGET logits, in front of ls_argmax_rows / ls_sample_rows (csrc/penalty.hip; no counterpart
+ * in the reference).  state [b, vocab] int32 (batch stride state_stride_b): bits 0-30 of a word = times the token was generated
+ * (first token included), bit 31 = the token occurs in the valid part of the prompt.  logits / out [b, rows, vocab] dtype with
+ * batch and row strides in elements; out == logits is allowed.  Row r of batch z adds to its history every extra_ids[z, c]
+ * (int64, batch stride ids_stride_b) with extra_mask[z, r, c] != 0 (int64, batch / row strides, unit column stride; a batch
+ * stride of 0 = one mask for every batch row), c < n_extra: a duplicate counts twice, an id outside [0, vocab) is ignored;
+ * n_extra = 0: no extras, both pointers may be NULL.  Per element v with 16-bit logit x, in fp32, every operation rounded once
+ * and never contracted, with c = count of v in the state + in the row's selected extras:
+ *   1. c > 0 or the prompt bit:  x = x / repetition when x > 0 (the correctly rounded IEEE quotient), else x = x * repetition
+ *   2. c > 0:                    t = frequency * float(c);  x = x - t;  x = x - presence
+ *   3. bias != NULL:             x = x + bias[v]            (bias [vocab] fp32; -inf bans a token)
+ *   4. out = x rounded to nearest-even in dtype (-inf stays -inf, an overflow becomes +-inf)
+ * One launch, no workspace, no atomics; a row's output depends on that row, its extras and the scalars only.
+ * LS_ERR_INVALID_ARG, before any launch: vocab or a stride not a multiple of 8, a row stride < vocab, logits / out / state / bias
+ * not 16-byte aligned, repetition <= 0 (or NaN), n_extra outside 0..1024. */
+int ls_penalize_rows(const void* logits, void* out, int b, int rows, int vocab, int dtype, int64_t in_stride_b, int64_t in_stride_r,
+                     int64_t out_stride_b, int64_t out_stride_r, const int32_t* state, int64_t state_stride_b,
+                     const int64_t* extra_ids, int64_t ids_stride_b, const int64_t* extra_mask, int64_t mask_stride_b,
+                     int64_t mask_stride_r, int n_extra, float repetition, float presence, float frequency, const float* bias,
+                     void* stream);
+
+/* Update of that state: for every ids[z, j] (int64, batch stride ids_stride_b), j < n and -- with num != NULL -- j <
+ * num[z * num_stride] (int64), inside [0, vocab): prompt == 0 adds 1 per occurrence (integer atomics: the same id three times in
+ * one call adds 3, bit 31 is never touched below 2^31 occurrences); prompt != 0 ORs bit 31 (idempotent, the count is not
+ * touched).  Ids outside the vocabulary -- zero padding aside, the out-of-vocabulary pad of the accepted-id row -- are ignored. */
+int ls_token_state_add(int32_t* state, int b, int vocab, int64_t state_stride_b, const int64_t* ids, int n, int64_t ids_stride_b,
+                       const int64_t* num, int64_t num_stride, int prompt, void* stream);
+
+/* ls_logprob_topk and ls_argmax_rows with the lm_head SHARDED BY VOCABULARY over the ranks of a node (no counterpart in the reference, which
  * replicates: llama_glide.py:474).  A "record" is what stage 1 produces per (8192-logit chunk, row): the chunk's max, its sum of
  * exp(x - max) and its k largest logits with their GLOBAL columns -- rows * (2 + 2k) floats per chunk slot, chunk-major.
  *   ls_topk_stage1   this rank's slice logits_local [rows, vocab_local] (global columns col_base .. , col_base a multiple of

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LONGSPEC_HIP_LIB") or os.path.join(HERE, "_lib", "liblongspec_hip.so")
 
 LS_F16, LS_BF16 = 0, 1
+LS_OK, LS_ERR_INVALID_ARG, LS_ERR_UNSUPPORTED, LS_ERR_WORKSPACE, LS_ERR_LAUNCH = 0, -1, -2, -3, -4
 LS_NEW_NONE, LS_NEW_FLASH, LS_NEW_TARGET, LS_NEW_DRAFT = 0, 1, 2, 3
 
 
@@ -92,6 +93,9 @@ SYMBOLS = {
     "ls_sample_workspace_bytes": (C.c_size_t, [_I, _I]),
     "ls_sample_rows": (C.c_int, [_P, _I, _I, _L, _I, _P, _P, C.c_uint64, C.c_float, _I, C.c_float, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                  _P]),
+    "ls_penalize_rows": (C.c_int, [_P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _L, _P, _L, _P, _L, _L, _I, C.c_float, C.c_float,
+                                   C.c_float, _P, _P]),
+    "ls_token_state_add": (C.c_int, [_P, _I, _I, _L, _P, _I, _L, _P, _L, _I, _P]),
     "ls_topk_chunk": (C.c_int, []),
     "ls_topk_stage1": (C.c_int, [_P, _I, _I, _L, _I, _I, _I, _I, _P, _P]),
     "ls_topk_stage2": (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),

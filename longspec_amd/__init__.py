@@ -7,3 +7,4 @@ from PyTorch-ROCm through the reference's own Python API (`LlamaGlide`,
 __version__ = "0.1.0"
 
 from .sampling import Sampling  # noqa: E402,F401
+from .penalties import Penalties  # noqa: E402,F401

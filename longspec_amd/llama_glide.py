@@ -23,6 +23,7 @@ from torch import nn
 
 from .graphs import GraphReplayer
 from .sampling import resolve as _resolve_sampling
+from .penalties import resolve as _resolve_penalties
 from .llama import (DecodeLinear, LlamaForCausalLM, LlamaMLP, LlamaRMSNorm, chunked_causal_prefill,
                     project_qkv, _default_ops)
 
@@ -353,8 +354,38 @@ class LlamaGlide(LlamaForCausalLM):
             streams = streams.view(bsz, 1).expand(bsz, logits.size(1))
         return self.ops.sample_rows(logits, positions, sampling, streams=streams)
 
-    def _first_token(self, logits, sampling, input_len):
-        """The prefill's token from ``logits`` [bsz, V] of prompt row ``input_len - 1``."""
+    def _token_state(self, bsz: int, device, prompt_ids=None, prompt_len=None):
+        """A fresh penalty state [bsz, V] int32 (``penalties.py``): bit 31 of a word = the token occurs in
+        ``prompt_ids[z, :prompt_len[z]]`` (``prompt_ids=None``: no flags, the synthetic-KV benchmark case), bits 0-30 (times
+        generated) zero."""
+        state = torch.zeros((bsz, self.lm_head.out_features), dtype=torch.int32, device=device)
+        if prompt_ids is not None:
+            num = None
+            if prompt_len is not None:
+                num = prompt_len.to(device=device, dtype=torch.int64).view(-1).expand(bsz).contiguous()
+            self.ops.token_state_add(state, prompt_ids.to(device=device, dtype=torch.int64), num=num, prompt=True)
+        return state
+
+    def _begin_penalties(self, st, penalties, bsz: int, device, prompt_ids, prompt_len, first_token, prompt_state=None):
+        """The penalty part of a decode state: ``st.penalties`` (resolved), ``st.token_state`` = the prompt's flags
+        (``prompt_state`` when the caller has built them already, for the first token) with ``first_token`` counted, and
+        ``st.bias_table``, the dense fp32 [V] bias on the device -- put there now, nothing is copied inside a graph capture.
+        Refused under a vocabulary-parallel shard."""
+        st.penalties, st.token_state, st.bias_table = penalties, None, None
+        if penalties is None:
+            return
+        sh = self.model.layers[-1].self_attn.shard
+        if sh is not None and sh.vocab_parallel:
+            raise ValueError("penalties= is not available with a vocabulary-parallel shard")
+        st.token_state = prompt_state if prompt_state is not None else self._token_state(bsz, device, prompt_ids, prompt_len)
+        self.ops.token_state_add(st.token_state, first_token.to(device=device, dtype=torch.int64).view(bsz, 1))
+        st.bias_table = penalties.bias_table(self.lm_head.out_features, device)
+
+    def _first_token(self, logits, sampling, input_len, penalties=None, prompt_state=None):
+        """The prefill's token from ``logits`` [bsz, V] of prompt row ``input_len - 1``; under ``penalties`` the history of
+        that row is the prompt alone (``prompt_state``: ``_token_state`` of the prompt)."""
+        if penalties is not None:
+            logits = self.ops.penalize_rows(logits, prompt_state, penalties)
         if sampling is None:
             return logits.argmax(dim=-1)
         positions = input_len.to(device=logits.device, dtype=torch.int64).view(-1) - 1
@@ -382,11 +413,14 @@ class LlamaGlide(LlamaForCausalLM):
         self.glide.cross_attn.shard = None
 
     @torch.inference_mode()
-    def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645, sampling=None):       # :552-585
+    def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645, sampling=None,
+                         penalties=None):                                                                          # :552-585
         """``sampling`` (``longspec_amd.Sampling``): every token is drawn from the target's filtered distribution instead of
-        taken as its arg-max -- the denominator of a sampled speculative run, and with the same seed the same text."""
+        taken as its arg-max -- the denominator of a sampled speculative run, and with the same seed the same text.
+        ``penalties`` (``longspec_amd.Penalties``): the logits of every step are penalised from the prompt and the text so far."""
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, None, use_env=True)
+        pen = _resolve_penalties(penalties, None, use_env=True)
         self._clear_shard()
         bsz = input_ids.size(0)
         output_ids = input_ids.new_zeros((bsz, max_gen_len))
@@ -397,7 +431,8 @@ class LlamaGlide(LlamaForCausalLM):
         hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
         input_len = prompt_length
         rows = torch.arange(bsz, device=input_ids.device)
-        output_ids[:, 0] = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), sampling, input_len)
+        pstate = self._token_state(bsz, input_ids.device, input_ids, input_len) if pen is not None else None
+        output_ids[:, 0] = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), sampling, input_len, pen, pstate)
         cache_lens += input_len.int()
         num = 0
         eos = self._stop_id(eos_id, "vanilla")
@@ -408,7 +443,8 @@ class LlamaGlide(LlamaForCausalLM):
         if on_gpu:
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record()
-        vs = self.begin_vanilla_decode(output_ids, cache_lens, input_len.int(), P, sampling=sampling)
+        vs = self.begin_vanilla_decode(output_ids, cache_lens, input_len.int(), P, sampling=sampling, penalties=penalties,
+                                       prompt_ids=input_ids, prompt_state=pstate)
         for step in range(1, max_gen_len):
             self.vanilla_step(vs)
             num += bsz
@@ -432,14 +468,20 @@ class LlamaGlide(LlamaForCausalLM):
         return output_ids, num, elapsed_time
 
     # ------------------------------------------------------------------------------------------
-    def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int, sampling=None):
+    def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int, sampling=None, penalties=None,
+                             prompt_ids=None, prompt_state=None):
         """State of the vanilla loop (``llama_glide.py:566-583``): ``output_ids`` [bsz, max_gen] with the first
         token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32.  ``sampling``:
-        draw instead of arg-max (None: the process-wide default LONGSPEC_SAMPLING, else greedy)."""
+        draw instead of arg-max (None: the process-wide default LONGSPEC_SAMPLING, else greedy).  ``penalties``: penalise
+        every step's logits (None: the process-wide default LONGSPEC_PENALTIES, else none) from ``vs.token_state``, which
+        starts from ``prompt_ids[z, :input_len[z]]`` (None: no prompt flags; ``prompt_state``: those flags, already built)
+        and the first token."""
         dev = output_ids.device
         sampling = _resolve_sampling(sampling, None, use_env=True)
+        penalties = _resolve_penalties(penalties, None, use_env=True)
         vs = _DecodeState(output_ids=output_ids, cache_lens=cache_lens, input_len=input_len, P=prompt_bound, step=0,
-                          rows=torch.arange(output_ids.size(0), device=dev), sampling=sampling)
+                          rows=torch.arange(output_ids.size(0), device=dev), sampling=sampling, penalties=penalties)
+        self._begin_penalties(vs, penalties, output_ids.size(0), dev, prompt_ids, input_len, output_ids[:, 0], prompt_state)
         vs.streams = torch.arange(output_ids.size(0), device=dev, dtype=torch.int32) if sampling is not None else None
         vs.use_graphs = bool(dev.type == "cuda" and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
         P = prompt_bound                                   # (the replayer holds no reference to the state that holds it)
@@ -452,9 +494,14 @@ class LlamaGlide(LlamaForCausalLM):
         cur = out[rows, (cl - il).long()].view(out.size(0), -1)
         hidden_states = self.model.forward(cur, cache_lens=cl, exec_type="decoding").last_hidden_state
         # (sampling: the row was rotated to position cl, the length before this step's increment)
-        llm_output = self._target_tokens(self.lm_head(hidden_states[:, -1, :]), vs.sampling, cl, vs.streams)
+        logits = self.lm_head(hidden_states[:, -1, :])
+        if vs.penalties is not None:
+            logits = self.ops.penalize_rows(logits, vs.token_state, vs.penalties, bias=vs.bias_table)
+        llm_output = self._target_tokens(logits, vs.sampling, cl, vs.streams)
         cl += 1
         out[rows, (cl - il).long()] = llm_output.view(-1)
+        if vs.penalties is not None:
+            self.ops.token_state_add(vs.token_state, llm_output.view(out.size(0), 1))
 
     def vanilla_step(self, vs):
         """Decode one token.  On a GPU the step is captured into a HIP graph after GRAPH_AFTER eager steps and replayed."""
@@ -480,18 +527,18 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def spec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                      sampling=None):                                                                              # :621-774
+                      sampling=None, penalties=None):                                                              # :621-774
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="glide",
-                                    sampling=sampling)
+                                    sampling=sampling, penalties=penalties)
 
     @torch.inference_mode()
     def magicdec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                          sampling=None):                                                                          # :776-913
+                          sampling=None, penalties=None):                                                          # :776-913
         """The MagicDec baseline of the reference's harness (``--method magicdec``): chain speculation where the
         drafter is the TARGET itself attending to a StreamingLLM cache (32 sink rows + the last 1024 prompt rows +
         what it generates), verified exactly like ``spec_generate``.  Same return tuple."""
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="magicdec",
-                                    sampling=sampling)
+                                    sampling=sampling, penalties=penalties)
 
     @torch.inference_mode()
     def vanilla_torch_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645):                      # :587-619
@@ -501,9 +548,11 @@ class LlamaGlide(LlamaForCausalLM):
         time flash-attn against eager attention)."""
         return self.vanilla_generate(input_ids, prompt_length, max_gen_len=max_gen_len, eos_id=eos_id)
 
-    def _chain_generate(self, input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter, sampling=None):
+    def _chain_generate(self, input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter, sampling=None,
+                        penalties=None):
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
+        pen = _resolve_penalties(penalties, temperature, use_env=True)
         magic = drafter == "magicdec"       # (temperature > 0: the same rejection block in both loops, :715-736 = :854-875)
         self._clear_shard()
         bsz = input_ids.size(0)
@@ -525,8 +574,10 @@ class LlamaGlide(LlamaForCausalLM):
             position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=cache_lens.clone(), llm_kv_len=cache_lens.clone(), exec_type="prefill")
-        st = self.begin_chain_decode(self._first_token(logits, sampling, input_len), cache_lens, input_len, P, gamma, max_gen_len,
-                                     eos_id, temperature, drafter, first_logits=logits, sampling=sampling)
+        pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
+        st = self.begin_chain_decode(self._first_token(logits, sampling, input_len, pen, pstate), cache_lens, input_len, P, gamma,
+                                     max_gen_len, eos_id, temperature, drafter, first_logits=logits, sampling=sampling,
+                                     penalties=penalties, prompt_ids=input_ids, prompt_state=pstate)
         _sync(input_ids)
         start_time = time.time()
         for out_index in range(1, max_gen_len):
@@ -537,21 +588,30 @@ class LlamaGlide(LlamaForCausalLM):
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
     def begin_chain_decode(self, first_token, cache_lens, input_len, prompt_bound: int, gamma=4, max_gen_len=64, eos_id=151645,
-                           temperature=0.0, drafter="glide", first_logits=None, sampling=None):
+                           temperature=0.0, drafter="glide", first_logits=None, sampling=None, penalties=None, prompt_ids=None,
+                           prompt_state=None):
         """State of the chain-speculation loop right after the prefills (``llama_glide.py:641-668``): ``first_token`` [bsz]
         = the target's first generated token, ``cache_lens`` [bsz] int32 = valid rows of every cache (the draft's included),
         ``input_len`` [bsz] = prompt length, ``prompt_bound`` = host-side bound of it.  Also the entry point of benchmarks
         that time ``chain_round`` on synthetic KV (bench.py --method seq).  ``sampling``: the verification pass draws its
         tokens instead of taking arg-maxes (None at temperature 0: the process-wide default LONGSPEC_SAMPLING, else greedy);
-        the drafter stays greedy."""
+        the drafter stays greedy.  ``penalties``: the verification rows are penalised, row i from ``st.token_state`` (the prompt
+        ``prompt_ids[z, :input_len[z]]``, None: no prompt flags, and the text so far) plus the i draft tokens it follows; the
+        drafter stays unpenalised."""
         bsz = first_token.size(0)
         dev = first_token.device
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
+        penalties = _resolve_penalties(penalties, temperature, use_env=True)
         if drafter != "magicdec":
             self._head_of_draft_passes()                # the draft passes' head and its pack exist before the first round
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
                              max_gen_len=max_gen_len, count=0, num=0, emitted=1, double_flag=False, sampling=sampling)
         st.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if sampling is not None else None
+        self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
+        st.chain_mask = None
+        if penalties is not None:
+            # verification row i follows the draft tokens spec_buffer[:, 1 : i + 1]
+            st.chain_mask = torch.ones((gamma + 1, gamma), dtype=torch.int64, device=dev).tril(-1)
         st.output_ids = first_token.new_zeros((bsz, max_gen_len + gamma))
         st.spec_mask = first_token.new_zeros((bsz, max_gen_len + gamma))
         st.output_ids[:, 0] = first_token
@@ -624,6 +684,9 @@ class LlamaGlide(LlamaForCausalLM):
                     spec_logits[:, spec_steps + 1, :] = current_logp
         hidden_states = self.model.forward(spec_buffer, cache_lens=cache_lens, exec_type="decoding").last_hidden_state
         llm_verify_logits = self.lm_head(hidden_states[:, -gamma - 1:, :])
+        if st.penalties is not None:
+            llm_verify_logits = self.ops.penalize_rows(llm_verify_logits, st.token_state, st.penalties, spec_buffer[:, 1:],
+                                                       st.chain_mask, bias=st.bias_table)
         # (sampling: verification row i was rotated to position cache_lens + i, models' forward :571-577)
         llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
                                                 cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
@@ -634,7 +697,10 @@ class LlamaGlide(LlamaForCausalLM):
         # acceptance by cumulative match, verified ids + bonus token -> output_ids, cache_lens += correct_len, the next
         # round's start tokens and draft_cache_lens = cache_lens - double_input (:738-770): one launch, one host read
         state = self.ops.chain_commit(llm_verify_output, spec_buffer, output_ids, cache_lens, draft_cache_lens, st.input_len_i32,
-                                      next_spec_start_token, st.eos, **({"accept_mask": accept} if accept is not None else {})).tolist()
+                                      next_spec_start_token, st.eos, **({"accept_mask": accept} if accept is not None else {}))
+        if st.penalties is not None:                         # the correct_len tokens this round wrote, before the host read
+            self.ops.token_state_add(st.token_state, llm_verify_output, num=state[:, 0])
+        state = state.tolist()
         n_ok, hit = state[0][0], any(row[1] for row in state)
         st.double_flag = n_ok == gamma + 1
         st.count += n_ok - 1
@@ -647,15 +713,20 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def tree_spec_generate(self, input_ids, prompt_length, tree_shape: Optional[List[int]] = None, max_gen_len=64,
-                           eos_id=151645, temperature=0.0, shard=None, sampling=None):        # :915-1126
+                           eos_id=151645, temperature=0.0, shard=None, sampling=None, penalties=None):        # :915-1126
         """``shard`` (``dist.KVShard``, every rank of the group calls with the same arguments): the prompt is prefilled
         and its KV kept sequence-sharded over the ranks (``_sharded_prefill``); decoding then runs replicated with one
         exchange per attention call.  Returns the same values on every rank.  ``sampling``: the verification pass draws
-        one token per row and the greedy acceptance runs on the draws (not with a vocabulary-parallel shard)."""
+        one token per row and the greedy acceptance runs on the draws (not with a vocabulary-parallel shard).  ``penalties``:
+        every verification row is penalised from its own history -- prompt, text so far and the tree path it follows (not with
+        a vocabulary-parallel shard; under a sequence shard every rank keeps the same state)."""
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
+        pen = _resolve_penalties(penalties, temperature, use_env=True)
         if sampling is not None and shard is not None and shard.vocab_parallel:
             raise ValueError("sampling= is not available with a vocabulary-parallel shard")
+        if pen is not None and shard is not None and shard.vocab_parallel:
+            raise ValueError("penalties= is not available with a vocabulary-parallel shard")
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
         dev = input_ids.device
@@ -669,23 +740,25 @@ class LlamaGlide(LlamaForCausalLM):
         for layer in self.model.layers:                    # a model object may be reused with and without a shard
             layer.self_attn.shard = shard
         self.glide.cross_attn.shard = shard
+        pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
         if shard is not None:
             if dev.type == "cuda" and not shard.peer_tried:
                 # a mailbox slot holds the record of the widest pass: 128 rows x heads x (128 + 1) floats
                 heads = max(self.config.num_attention_heads, self.glide.config.num_attention_heads)
                 shard.enable_peer_exchange(bsz * 128 * heads * 129, dev)
-            first = self._sharded_prefill(input_ids, input_len, position_ids, shard, sampling)
+            first = self._sharded_prefill(input_ids, input_len, position_ids, shard, sampling, pen, pstate)
         else:
             # prefill LLM (:954-960)
             self._set_hints(P, P)
             hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
-            first = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), sampling, input_len)
+            first = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), sampling, input_len, pen, pstate)
             # prefill glide (:968-975)
             hidden_states = self.model.embed_tokens(input_ids)
             position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=lens.clone(), llm_kv_len=lens.clone(), exec_type="prefill")
-        st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature, sampling=sampling)
+        st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature, sampling=sampling,
+                                    penalties=penalties, prompt_ids=input_ids, prompt_state=pstate)
         _sync(input_ids)
         start_time = time.time()
         for out_index in range(1, max_gen_len):
@@ -702,7 +775,7 @@ class LlamaGlide(LlamaForCausalLM):
             shard.raise_if_exchange_failed()
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
-    def _sharded_prefill(self, input_ids, input_len, position_ids, shard, sampling=None):
+    def _sharded_prefill(self, input_ids, input_len, position_ids, shard, sampling=None, penalties=None, prompt_state=None):
         """Sequence-sharded prefill: rank r runs the target model on prompt rows [r*Ls, (r+1)*Ls) only
         (one all-gather of the layer's K/V rows per layer, ``LlamaAttention.sharded_prefill``) and keeps that slice of the
         KV; the tail rank computes the first token and broadcasts it.  The draft layer's cache is filled on every rank
@@ -726,22 +799,26 @@ class LlamaGlide(LlamaForCausalLM):
             shard.prefill_ctx = None
         first = torch.zeros((bsz,), dtype=torch.int64, device=input_ids.device)
         if shard.is_tail:
-            first = self._first_token(self.lm_head(hidden_states[:, hi - lo - 1, :]), sampling, input_len)
+            first = self._first_token(self.lm_head(hidden_states[:, hi - lo - 1, :]), sampling, input_len, penalties, prompt_state)
         shard.broadcast_from_tail(first)
         hidden_states = self.model.embed_tokens(input_ids)
         self.glide.prefill_cache_only(hidden_states, self.model.rotary_emb(hidden_states, position_ids))
         return first
 
     def begin_tree_decode(self, first_token, cache_lens, prompt_bound: int, tree_shape=None, max_gen_len=64, eos_id=151645,
-                          temperature=0.0, sampling=None):
+                          temperature=0.0, sampling=None, penalties=None, prompt_ids=None, prompt_state=None):
         """State of the round loop right after the two prefills (``llama_glide.py:927-991``).
         ``first_token`` [bsz] = the target's first generated token, ``cache_lens`` [bsz] int32 = valid
         rows of every KV cache, ``prompt_bound`` = host-side bound of it.  Also the entry point of
         synthetic-KV benchmarks, which fill the caches themselves instead of prefilling.  ``sampling``: the round is the
         temperature-0 round with the arg-max of the verification logits replaced by one draw per row (None at temperature 0:
-        the process-wide default LONGSPEC_SAMPLING, else greedy)."""
+        the process-wide default LONGSPEC_SAMPLING, else greedy).  ``penalties``: the verification rows are penalised in front
+        of that arg-max or draw, row j from ``st.token_state`` (``prompt_ids[z, :cache_lens[z]]``, None: no prompt flags, and
+        the text so far) plus the tokens on node j's path (None at temperature 0: the process-wide default
+        LONGSPEC_PENALTIES, else none)."""
         dev = first_token.device
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
+        penalties = _resolve_penalties(penalties, temperature, use_env=True)
         sh = self.model.layers[-1].self_attn.shard
         if sampling is not None and sh is not None and sh.vocab_parallel:
             raise ValueError("sampling= is not available with a vocabulary-parallel shard")
@@ -755,6 +832,7 @@ class LlamaGlide(LlamaForCausalLM):
         R = Fn - 1 + gamma + 1               # verification rows: [a accepted | F-1 tree | pads]
         self._head_of_draft_passes()                    # the draft passes' head and its pack exist before the first warm-up round
         st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz, sampling=sampling)
+        self._begin_penalties(st, penalties, bsz, dev, prompt_ids, cache_lens, first_token, prompt_state)
         st.output_ids = torch.full((bsz, max_gen_len), self._tree_output_fill(eos_id), dtype=torch.int64, device=dev)  # :937 (G8)
         st.spec_mask = torch.zeros((bsz, max_gen_len), dtype=torch.int64, device=dev)
         st.output_ids[:, 0] = first_token
@@ -867,7 +945,7 @@ class LlamaGlide(LlamaForCausalLM):
             return
         st.graphs_forced = True
         names = ("cache_lens", "target_cache_lens_for_draft", "draft_cache_lens", "tree_mask", "all_spec", "history_logp_sum",
-                 "acc_pad", "output_ids", "emitted_dev")
+                 "acc_pad", "output_ids", "emitted_dev") + (("token_state",) if st.token_state is not None else ())
         with rp.guard():
             rp.roll_over(st.emitted)
             for a in range(1, st.gamma + 2):
@@ -958,7 +1036,12 @@ class LlamaGlide(LlamaForCausalLM):
             all_llm_pred = vsh.head_select(self.lm_head, hidden_states, ops, argmax=True).view(bsz, -1)
         else:
             # (sampling: rows a-1 .. a+Fn-2 of the pass, at the positions ops.tree_verify_inputs gave RoPE for them)
-            all_llm_pred = self._target_tokens(self.lm_head(hidden_states), st.sampling,
+            llm_logits = self.lm_head(hidden_states)
+            if st.penalties is not None:
+                # row j follows the committed text (the root included) and the nodes on its path: mask row j, root column aside
+                llm_logits = ops.penalize_rows(llm_logits, st.token_state, st.penalties, all_spec[:, 1:], tree_mask[:, :, 1:],
+                                               bias=st.bias_table)
+            all_llm_pred = self._target_tokens(llm_logits, st.sampling,
                                                position_ids[:, a - 1:a + Fn - 1] if st.sampling is not None else None)
         # ---- A: accept / reject tree collapse + last-layer KV row move (:1104-1116); the accepted rows start at
         # cache_lens + a - 1 (:1104), the cache lengths themselves advance in the commit below
@@ -974,9 +1057,12 @@ class LlamaGlide(LlamaForCausalLM):
         # emitted tokens -> output_ids (at the device-side offset), the EOS test on the whole buffer as the reference
         # does (:1120, G8), the tree state reset and `cache_lens += a`, `target_cache_lens_for_draft += acc_num`
         # (:1104-1117): one launch; its result is the round's ONE host read for (acc_num, eos flag)
-        return ops.tree_commit(acc_pad, acc_num_t, st.output_ids, 0, st.eos, tree_mask, all_spec, history_logp_sum,
-                               target_lens=st.cache_lens, target_add=a, draft_kv_lens=st.target_cache_lens_for_draft,
-                               emitted_dev=st.emitted_dev)
+        state = ops.tree_commit(acc_pad, acc_num_t, st.output_ids, 0, st.eos, tree_mask, all_spec, history_logp_sum,
+                                target_lens=st.cache_lens, target_add=a, draft_kv_lens=st.target_cache_lens_for_draft,
+                                emitted_dev=st.emitted_dev)
+        if st.penalties is not None:                          # the accepted tokens, inside the round (and its graph)
+            ops.token_state_add(st.token_state, acc_pad, num=acc_num_t)
+        return state
 
     def tree_round_stochastic(self, st) -> bool:
         """One round at temperature > 0 (``llama_glide.py:997-1102,1110-1121``).  The draft passes and the verification pass

@@ -13,6 +13,8 @@ One function per reference seam of the draft-then-verify round:
                          (logp_out=: the draft's log-prob table of the temperature > 0 rounds, :1025,1074)
   sample_rows            one draw per row from the target's tempered, top-k / top-p filtered distribution (sampling=;
                          no counterpart in the reference)
+  penalize_rows / token_state_add   repetition / presence / frequency penalties and a logit bias on the target's logits, per
+                         row from that row's own history, and the [batch, vocab] state they read (penalties=; no counterpart)
   tree_commit / tree_commit_stochastic   end of a round at temperature 0 / > 0  llama_glide.py:1093-1121
   linear / linear_multi / mlp_gate_up   the projections of a decode pass (M <= 80 token rows):
                          q/k/v/o_proj llama.py:361-363,390, LlamaMLP (qwen2.py:218-230), lm_head llama_glide.py:1091
@@ -398,6 +400,75 @@ def sample_rows(logits: torch.Tensor, positions: torch.Tensor, sampling, streams
     if return_top2:
         return out.view(shape), t2i.view(*shape, 2), t2k.view(*shape, 2), kept.view(shape), thr.view(shape)
     return out.view(shape)
+
+
+def penalize_rows(logits: torch.Tensor, state: torch.Tensor, penalties, extra_ids: Optional[torch.Tensor] = None,
+                  extra_mask: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """TARGET logits [b, V] or [b, R, V] rewritten under ``penalties`` (``longspec_amd.Penalties``) from each row's history
+    (``ls_penalize_rows``): ``state`` [b, V] int32 (bits 0-30 = times generated, bit 31 = in the prompt) plus, for row r of
+    batch z, every ``extra_ids[z, c]`` (int64 [b, C]) with ``extra_mask[z, r, c] != 0`` (int64 [b, R, C], or [R, C] = one mask
+    for the whole batch).  ``bias``: ``penalties.bias_table(V, device)`` when the caller keeps it (the decode loops do: the
+    table is not rebuilt per call, and never inside a graph capture); None: built here.  Returns a NEW contiguous tensor of the input's shape and dtype: what follows (``argmax_rows``,
+    ``sample_rows``) reads it as it is, whatever the input aliased."""
+    _dev(logits, state, extra_ids, extra_mask)
+    shape = logits.shape
+    V = shape[-1]
+    if logits.dim() not in (2, 3):
+        raise ValueError("penalize_rows: logits [b, V] or [b, R, V]")
+    x = logits if logits.dim() == 3 else logits.unsqueeze(1)
+    b, R = x.shape[0], x.shape[1]
+    if x.stride(2) != 1 or x.stride(0) % 8 != 0 or x.stride(1) % 8 != 0 or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    if state.dtype != torch.int32 or tuple(state.shape) != (b, V) or state.stride(1) != 1:
+        raise TypeError(f"penalize_rows: state must be int32 [{b}, {V}] with contiguous rows")
+    C = 0
+    ids_p = mask_p = None
+    ids_sb = mask_sb = mask_sr = 0
+    if extra_ids is not None and extra_ids.shape[-1] > 0:
+        if extra_mask is None:
+            raise ValueError("penalize_rows: extra_ids needs extra_mask")
+        C = extra_ids.shape[-1]
+        if extra_ids.dtype != torch.int64 or extra_ids.dim() != 2 or extra_ids.shape[0] != b or extra_ids.stride(1) != 1:
+            raise TypeError("penalize_rows: extra_ids must be int64 [b, C] with contiguous rows")
+        if extra_mask.dtype != torch.int64 or extra_mask.stride(-1) != 1 or tuple(extra_mask.shape[-2:]) != (R, C) \
+                or (extra_mask.dim() == 3 and extra_mask.shape[0] != b) or extra_mask.dim() not in (2, 3):
+            raise TypeError("penalize_rows: extra_mask must be int64 [b, R, C] or [R, C] with unit column stride")
+        ids_p, ids_sb = extra_ids.data_ptr(), extra_ids.stride(0)
+        mask_p, mask_sr = extra_mask.data_ptr(), extra_mask.stride(-2)
+        mask_sb = extra_mask.stride(0) if extra_mask.dim() == 3 else 0
+    out = torch.empty((b, R, V), dtype=x.dtype, device=x.device)
+    if bias is None:
+        bias = penalties.bias_table(V, x.device)
+    elif bias.dtype != torch.float32 or tuple(bias.shape) != (V,) or not bias.is_contiguous() or bias.device != x.device:
+        raise TypeError(f"penalize_rows: bias must be a contiguous fp32 [{V}] tensor on the logits' device")
+    _C.check(_C.load().ls_penalize_rows(x.data_ptr(), out.data_ptr(), b, R, V, _dtype(x), x.stride(0), x.stride(1), out.stride(0),
+                                        out.stride(1), state.data_ptr(), state.stride(0), ids_p, ids_sb, mask_p, mask_sb, mask_sr, C,
+                                        penalties.repetition, penalties.presence, penalties.frequency,
+                                        bias.data_ptr() if bias is not None else None, _stream()), "ls_penalize_rows")
+    return out.view(shape)
+
+
+def token_state_add(state: torch.Tensor, ids: torch.Tensor, num: Optional[torch.Tensor] = None, prompt: bool = False) -> None:
+    """Update the penalty state [b, V] int32 in place (``ls_token_state_add``): every ``ids[z, j]`` (int64 [b, n]) with
+    ``j < num[z]`` (``num`` [b] int64, None: all) inside the vocabulary adds 1 to its word's count, or -- ``prompt`` -- sets
+    bit 31.  Ids outside [0, V) are ignored."""
+    _dev(state, ids, num)
+    if state.dtype != torch.int32 or state.dim() != 2 or state.stride(1) != 1:
+        raise TypeError("token_state_add: state must be int32 [b, V] with contiguous rows")
+    b, V = state.shape
+    if ids.dim() == 1:
+        ids = ids.view(b, -1)
+    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] != b:
+        raise TypeError("token_state_add: ids must be int64 [b, n]")
+    if ids.shape[1] > 1 and ids.stride(1) != 1:
+        ids = ids.contiguous()
+    num_p, num_s = None, 0
+    if num is not None:
+        if num.dtype != torch.int64 or num.numel() != b or num.dim() != 1:
+            raise TypeError("token_state_add: num must be int64 [b]")
+        num_p, num_s = num.data_ptr(), num.stride(0)
+    _C.check(_C.load().ls_token_state_add(state.data_ptr(), b, V, state.stride(0), ids.data_ptr(), ids.shape[1], ids.stride(0),
+                                          num_p, num_s, 1 if prompt else 0, _stream()), "ls_token_state_add")
 
 
 TOPK_CHUNK = 8192          # logits per stage-1 record (ls_topk_chunk(); checked at first use)
