@@ -387,6 +387,36 @@ int ls_penalize_rows(const void* logits, void* out, int b, int rows, int vocab, 
 int ls_token_state_add(int32_t* state, int b, int vocab, int64_t state_stride_b, const int64_t* ids, int n, int64_t ids_stride_b,
                        const int64_t* num, int64_t num_stride, int prompt, void* stream);
 
+/* Log-probabilities of emitted tokens and their top-n alternatives (logprobs=; csrc/logprob.hip; no counterpart in the reference).
+ * logits [b, rows, vocab] dtype with batch and row strides in elements: the TARGET's logits as the token was picked from them,
+ * i.e. behind ls_penalize_rows.  ids [b, rows] int64 (batch stride ids_stride_b): the chosen column of every row.  Per row, in
+ * fp32 with every operation rounded once, m = max_i x_i and lse = ln sum_i exp((x_i - m) / temperature):
+ *   lp_j = (x_j - m) / temperature - lse
+ * over the FULL vocabulary -- the tempered (and penalised) soft-max, not the set a top-k / top-p cut of the sampler keeps.
+ *   row_lp      [b, rows] fp32      lp of the chosen column; NaN for an id outside [0, vocab); -inf for a -inf logit
+ *   row_top_val [b, rows, n] fp32   lp of the n columns with the largest logits, ordered by (logit descending, column ascending)
+ *   row_top_idx [b, rows, n] int64  with -0.0 == +0.0 (the order of ls_argmax_rows), their columns; a row with fewer than n columns
+ *                                   is padded with (-inf, -1).  Both NULL when n == 0.
+ * Equal logits of a row get bit-equal values, and row_lp is bit-equal to the chosen column's list entry when it is listed.  A row
+ * whose maximum is -inf gives NaN.  A row's outputs depend on that row, its id, temperature and n only.  Two launches: (chunks of
+ * 8192 columns, rows * b) workgroups write one record each (max, sum, n candidates) into the workspace, one workgroup per row
+ * merges them in chunk order; no floating-point atomics.  LS_ERR_INVALID_ARG, before any launch: vocab or a stride not a multiple
+ * of 8, a row stride < vocab, misaligned pointers (logits 16 bytes), temperature <= 0 (or NaN, or infinite), n outside 0..20,
+ * rows * b outside 1..1024.  LS_ERR_UNSUPPORTED: vocab > 524288. */
+size_t ls_token_logprobs_workspace_bytes(int b, int rows, int vocab, int n);
+int ls_token_logprobs(const void* logits, int b, int rows, int vocab, int dtype, int64_t stride_b, int64_t stride_r,
+                      const int64_t* ids, int64_t ids_stride_b, float temperature, int n, float* row_lp, float* row_top_val,
+                      int64_t* row_top_idx, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The rows a round accepted -> the output columns of the tokens they produced (one launch, one workgroup per batch row).  For
+ * j < num[z * num_stride] (int64; num == NULL: every j < max_rows):  src = map ? map[z, j] : j  (map int64 [b, max_rows]),
+ * dst = base[z] + base_add + j  (base int32 [b], on the device);  row_lp[z, src] -> out_token[z, dst] and the n-vectors
+ * row_top_val / row_top_idx [z, src, :] -> out_top_val / out_top_idx [z, dst, :]  (out_* [b, out_cap(, n)], dense).  src outside
+ * [0, rows) and dst outside [0, out_cap) are skipped, never written.  n == 0: the four top-n pointers may be NULL. */
+int ls_logprob_commit(const float* row_lp, const float* row_top_val, const int64_t* row_top_idx, int b, int rows, int n,
+                      const int64_t* map, int max_rows, const int64_t* num, int64_t num_stride, const int32_t* base, int base_add,
+                      float* out_token, float* out_top_val, int64_t* out_top_idx, int out_cap, void* stream);
+
 /* ls_logprob_topk and ls_argmax_rows with the lm_head SHARDED BY VOCABULARY over the ranks of a node (no counterpart in the reference, which
  * replicates: llama_glide.py:474).  A "record" is what stage 1 produces per (8192-logit chunk, row): the chunk's max, its sum of
  * exp(x - max) and its k largest logits with their GLOBAL columns -- rows * (2 + 2k) floats per chunk slot, chunk-major.

@@ -24,6 +24,7 @@ from torch import nn
 from .graphs import GraphReplayer
 from .sampling import resolve as _resolve_sampling
 from .penalties import resolve as _resolve_penalties
+from .logprobs import new_buffers as _logprob_buffers, resolve as _resolve_logprobs
 from .llama import (DecodeLinear, LlamaForCausalLM, LlamaMLP, LlamaRMSNorm, chunked_causal_prefill,
                     project_qkv, _default_ops)
 
@@ -381,15 +382,39 @@ class LlamaGlide(LlamaForCausalLM):
         self.ops.token_state_add(st.token_state, first_token.to(device=device, dtype=torch.int64).view(bsz, 1))
         st.bias_table = penalties.bias_table(self.lm_head.out_features, device)
 
-    def _first_token(self, logits, sampling, input_len, penalties=None, prompt_state=None):
+    def _begin_logprobs(self, st, logprobs, bsz: int, width: int, device, first=None):
+        """The log-prob part of a decode state: ``st.logprobs`` = None, or the namespace of ``logprobs.py`` -- ``token``
+        [bsz, width], ``top_ids`` / ``top`` [bsz, width, top_n], aligned column for column with ``st.output_ids`` and holding
+        their fill values -- plus ``top_n`` and ``temperature``, the sampler's (1 for greedy decoding).  ``first``: the rows of
+        the first token (``_first_token``), written to column 0; None (a caller that starts from synthetic caches): column 0
+        keeps the fill.  Refused under a vocabulary-parallel shard."""
+        st.logprobs = None
+        if logprobs is None:
+            return
+        sh = self.model.layers[-1].self_attn.shard
+        if sh is not None and sh.vocab_parallel:
+            raise ValueError("logprobs= is not available with a vocabulary-parallel shard")
+        lp = _logprob_buffers(bsz, width, logprobs.top_n, device)
+        lp.top_n = logprobs.top_n
+        lp.temperature = st.sampling.temperature if st.sampling is not None else 1.0
+        if first is not None:
+            lp.token[:, 0], lp.top[:, 0], lp.top_ids[:, 0] = first[0][:, 0], first[1][:, 0], first[2][:, 0]
+        st.logprobs = lp
+
+    def _first_token(self, logits, sampling, input_len, penalties=None, prompt_state=None, logprobs=None):
         """The prefill's token from ``logits`` [bsz, V] of prompt row ``input_len - 1``; under ``penalties`` the history of
-        that row is the prompt alone (``prompt_state``: ``_token_state`` of the prompt)."""
+        that row is the prompt alone (``prompt_state``: ``_token_state`` of the prompt).  Returns (token, its log-prob rows
+        (``ops.token_logprobs``) under ``logprobs``, else None)."""
         if penalties is not None:
             logits = self.ops.penalize_rows(logits, prompt_state, penalties)
         if sampling is None:
-            return logits.argmax(dim=-1)
-        positions = input_len.to(device=logits.device, dtype=torch.int64).view(-1) - 1
-        return self._target_tokens(logits, sampling, positions)
+            token = logits.argmax(dim=-1)
+        else:
+            positions = input_len.to(device=logits.device, dtype=torch.int64).view(-1) - 1
+            token = self._target_tokens(logits, sampling, positions)
+        if logprobs is None:
+            return token, None
+        return token, self.ops.token_logprobs(logits, token, sampling.temperature if sampling is not None else 1.0, logprobs.top_n)
 
     def _stop_id(self, eos_id, loop: str):
         """Token whose appearance ends a loop.  The Llama twin tests ``self.config.eos_token_id`` in all
@@ -414,13 +439,17 @@ class LlamaGlide(LlamaForCausalLM):
 
     @torch.inference_mode()
     def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645, sampling=None,
-                         penalties=None):                                                                          # :552-585
+                         penalties=None, logprobs=None):                                                           # :552-585
         """``sampling`` (``longspec_amd.Sampling``): every token is drawn from the target's filtered distribution instead of
         taken as its arg-max -- the denominator of a sampled speculative run, and with the same seed the same text.
-        ``penalties`` (``longspec_amd.Penalties``): the logits of every step are penalised from the prompt and the text so far."""
+        ``penalties`` (``longspec_amd.Penalties``): the logits of every step are penalised from the prompt and the text so far.
+        ``logprobs`` (``longspec_amd.Logprobs``): the log-prob of every token under the distribution it was taken from and its
+        top-n alternatives, published as ``self.last_logprobs`` (``logprobs.py``; None without it); the return tuple is
+        unchanged."""
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, None, use_env=True)
         pen = _resolve_penalties(penalties, None, use_env=True)
+        lpc = _resolve_logprobs(logprobs, None, use_env=True)
         self._clear_shard()
         bsz = input_ids.size(0)
         output_ids = input_ids.new_zeros((bsz, max_gen_len))
@@ -432,7 +461,8 @@ class LlamaGlide(LlamaForCausalLM):
         input_len = prompt_length
         rows = torch.arange(bsz, device=input_ids.device)
         pstate = self._token_state(bsz, input_ids.device, input_ids, input_len) if pen is not None else None
-        output_ids[:, 0] = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), sampling, input_len, pen, pstate)
+        output_ids[:, 0], first_lp = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), sampling, input_len,
+                                                       pen, pstate, lpc)
         cache_lens += input_len.int()
         num = 0
         eos = self._stop_id(eos_id, "vanilla")
@@ -444,7 +474,8 @@ class LlamaGlide(LlamaForCausalLM):
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record()
         vs = self.begin_vanilla_decode(output_ids, cache_lens, input_len.int(), P, sampling=sampling, penalties=penalties,
-                                       prompt_ids=input_ids, prompt_state=pstate)
+                                       prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp)
+        self.last_logprobs = vs.logprobs
         for step in range(1, max_gen_len):
             self.vanilla_step(vs)
             num += bsz
@@ -463,25 +494,31 @@ class LlamaGlide(LlamaForCausalLM):
         elapsed_time = time.time() - start_time
         if eos is not None:
             output_ids, num, stop = _truncate_after_eos_vanilla(output_ids, num, eos, bsz)
+            if stop is not None and vs.logprobs is not None:          # the cut of output_ids, on its columns
+                lp = vs.logprobs
+                lp.token[:, stop + 1:], lp.top_ids[:, stop + 1:], lp.top[:, stop + 1:] = float("nan"), -1, float("-inf")
             if stop is not None and stop < len(marks):
                 elapsed_time = ev0.elapsed_time(marks[stop - 1]) * 1e-3 if on_gpu else marks[stop - 1]
         return output_ids, num, elapsed_time
 
     # ------------------------------------------------------------------------------------------
     def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int, sampling=None, penalties=None,
-                             prompt_ids=None, prompt_state=None):
+                             prompt_ids=None, prompt_state=None, logprobs=None, first_logprobs=None):
         """State of the vanilla loop (``llama_glide.py:566-583``): ``output_ids`` [bsz, max_gen] with the first
         token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32.  ``sampling``:
         draw instead of arg-max (None: the process-wide default LONGSPEC_SAMPLING, else greedy).  ``penalties``: penalise
         every step's logits (None: the process-wide default LONGSPEC_PENALTIES, else none) from ``vs.token_state``, which
         starts from ``prompt_ids[z, :input_len[z]]`` (None: no prompt flags; ``prompt_state``: those flags, already built)
-        and the first token."""
+        and the first token.  ``logprobs``: every step also fills its column of ``vs.logprobs`` (None: the process-wide
+        default LONGSPEC_LOGPROBS, else none; ``first_logprobs``: the first token's rows, for column 0)."""
         dev = output_ids.device
         sampling = _resolve_sampling(sampling, None, use_env=True)
         penalties = _resolve_penalties(penalties, None, use_env=True)
+        logprobs = _resolve_logprobs(logprobs, None, use_env=True)
         vs = _DecodeState(output_ids=output_ids, cache_lens=cache_lens, input_len=input_len, P=prompt_bound, step=0,
                           rows=torch.arange(output_ids.size(0), device=dev), sampling=sampling, penalties=penalties)
         self._begin_penalties(vs, penalties, output_ids.size(0), dev, prompt_ids, input_len, output_ids[:, 0], prompt_state)
+        self._begin_logprobs(vs, logprobs, output_ids.size(0), output_ids.size(1), dev, first_logprobs)
         vs.streams = torch.arange(output_ids.size(0), device=dev, dtype=torch.int32) if sampling is not None else None
         vs.use_graphs = bool(dev.type == "cuda" and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
         P = prompt_bound                                   # (the replayer holds no reference to the state that holds it)
@@ -500,6 +537,10 @@ class LlamaGlide(LlamaForCausalLM):
         llm_output = self._target_tokens(logits, vs.sampling, cl, vs.streams)
         cl += 1
         out[rows, (cl - il).long()] = llm_output.view(-1)
+        if vs.logprobs is not None:                          # the token's row -> the column it was written to
+            lp = vs.logprobs
+            self.ops.logprob_commit(self.ops.token_logprobs(logits, llm_output.view(-1), lp.temperature, lp.top_n), lp,
+                                    (cl - il).to(torch.int32))
         if vs.penalties is not None:
             self.ops.token_state_add(vs.token_state, llm_output.view(out.size(0), 1))
 
@@ -527,18 +568,18 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def spec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                      sampling=None, penalties=None):                                                              # :621-774
+                      sampling=None, penalties=None, logprobs=None):                                               # :621-774
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="glide",
-                                    sampling=sampling, penalties=penalties)
+                                    sampling=sampling, penalties=penalties, logprobs=logprobs)
 
     @torch.inference_mode()
     def magicdec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                          sampling=None, penalties=None):                                                          # :776-913
+                          sampling=None, penalties=None, logprobs=None):                                           # :776-913
         """The MagicDec baseline of the reference's harness (``--method magicdec``): chain speculation where the
         drafter is the TARGET itself attending to a StreamingLLM cache (32 sink rows + the last 1024 prompt rows +
         what it generates), verified exactly like ``spec_generate``.  Same return tuple."""
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="magicdec",
-                                    sampling=sampling, penalties=penalties)
+                                    sampling=sampling, penalties=penalties, logprobs=logprobs)
 
     @torch.inference_mode()
     def vanilla_torch_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645):                      # :587-619
@@ -549,10 +590,11 @@ class LlamaGlide(LlamaForCausalLM):
         return self.vanilla_generate(input_ids, prompt_length, max_gen_len=max_gen_len, eos_id=eos_id)
 
     def _chain_generate(self, input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter, sampling=None,
-                        penalties=None):
+                        penalties=None, logprobs=None):
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         pen = _resolve_penalties(penalties, temperature, use_env=True)
+        lpc = _resolve_logprobs(logprobs, temperature, use_env=True)
         magic = drafter == "magicdec"       # (temperature > 0: the same rejection block in both loops, :715-736 = :854-875)
         self._clear_shard()
         bsz = input_ids.size(0)
@@ -575,9 +617,11 @@ class LlamaGlide(LlamaForCausalLM):
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=cache_lens.clone(), llm_kv_len=cache_lens.clone(), exec_type="prefill")
         pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
-        st = self.begin_chain_decode(self._first_token(logits, sampling, input_len, pen, pstate), cache_lens, input_len, P, gamma,
-                                     max_gen_len, eos_id, temperature, drafter, first_logits=logits, sampling=sampling,
-                                     penalties=penalties, prompt_ids=input_ids, prompt_state=pstate)
+        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc)
+        st = self.begin_chain_decode(first, cache_lens, input_len, P, gamma, max_gen_len, eos_id, temperature, drafter,
+                                     first_logits=logits, sampling=sampling, penalties=penalties, prompt_ids=input_ids,
+                                     prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp)
+        self.last_logprobs = st.logprobs
         _sync(input_ids)
         start_time = time.time()
         for out_index in range(1, max_gen_len):
@@ -589,7 +633,7 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_chain_decode(self, first_token, cache_lens, input_len, prompt_bound: int, gamma=4, max_gen_len=64, eos_id=151645,
                            temperature=0.0, drafter="glide", first_logits=None, sampling=None, penalties=None, prompt_ids=None,
-                           prompt_state=None):
+                           prompt_state=None, logprobs=None, first_logprobs=None):
         """State of the chain-speculation loop right after the prefills (``llama_glide.py:641-668``): ``first_token`` [bsz]
         = the target's first generated token, ``cache_lens`` [bsz] int32 = valid rows of every cache (the draft's included),
         ``input_len`` [bsz] = prompt length, ``prompt_bound`` = host-side bound of it.  Also the entry point of benchmarks
@@ -597,11 +641,13 @@ class LlamaGlide(LlamaForCausalLM):
         tokens instead of taking arg-maxes (None at temperature 0: the process-wide default LONGSPEC_SAMPLING, else greedy);
         the drafter stays greedy.  ``penalties``: the verification rows are penalised, row i from ``st.token_state`` (the prompt
         ``prompt_ids[z, :input_len[z]]``, None: no prompt flags, and the text so far) plus the i draft tokens it follows; the
-        drafter stays unpenalised."""
+        drafter stays unpenalised.  ``logprobs``: the rows a round accepts fill their columns of ``st.logprobs`` (None at
+        temperature 0: the process-wide default LONGSPEC_LOGPROBS, else none; ``first_logprobs``: the first token's rows)."""
         bsz = first_token.size(0)
         dev = first_token.device
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         penalties = _resolve_penalties(penalties, temperature, use_env=True)
+        logprobs = _resolve_logprobs(logprobs, temperature, use_env=True)
         if drafter != "magicdec":
             self._head_of_draft_passes()                # the draft passes' head and its pack exist before the first round
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
@@ -612,6 +658,7 @@ class LlamaGlide(LlamaForCausalLM):
         if penalties is not None:
             # verification row i follows the draft tokens spec_buffer[:, 1 : i + 1]
             st.chain_mask = torch.ones((gamma + 1, gamma), dtype=torch.int64, device=dev).tril(-1)
+        self._begin_logprobs(st, logprobs, bsz, max_gen_len + gamma, dev, first_logprobs)
         st.output_ids = first_token.new_zeros((bsz, max_gen_len + gamma))
         st.spec_mask = first_token.new_zeros((bsz, max_gen_len + gamma))
         st.output_ids[:, 0] = first_token
@@ -690,6 +737,12 @@ class LlamaGlide(LlamaForCausalLM):
         # (sampling: verification row i was rotated to position cache_lens + i, models' forward :571-577)
         llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
                                                 cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
+        lp_rows = lp_base = None
+        if st.logprobs is not None:
+            # every verification row's token under the distribution it was taken from; the commit below keeps a prefix of
+            # them, at the columns behind cache_lens - input_len as it stands BEFORE chain_commit advances it
+            lp_rows = self.ops.token_logprobs(llm_verify_logits, llm_verify_output, st.logprobs.temperature, st.logprobs.top_n)
+            lp_base = (cache_lens - st.input_len_i32).to(torch.int32)
         accept = None
         if st.temperature > 0:                               # :715-736
             llm_verify_output, accept = self.ops.chain_accept_stochastic(spec_logits, llm_verify_logits, spec_buffer,
@@ -700,6 +753,8 @@ class LlamaGlide(LlamaForCausalLM):
                                       next_spec_start_token, st.eos, **({"accept_mask": accept} if accept is not None else {}))
         if st.penalties is not None:                         # the correct_len tokens this round wrote, before the host read
             self.ops.token_state_add(st.token_state, llm_verify_output, num=state[:, 0])
+        if lp_rows is not None:                              # ... and their log-probs, to the columns chain_commit wrote
+            self.ops.logprob_commit(lp_rows, st.logprobs, lp_base, base_add=1, num=state[:, 0])
         state = state.tolist()
         n_ok, hit = state[0][0], any(row[1] for row in state)
         st.double_flag = n_ok == gamma + 1
@@ -713,20 +768,26 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def tree_spec_generate(self, input_ids, prompt_length, tree_shape: Optional[List[int]] = None, max_gen_len=64,
-                           eos_id=151645, temperature=0.0, shard=None, sampling=None, penalties=None):        # :915-1126
+                           eos_id=151645, temperature=0.0, shard=None, sampling=None, penalties=None,
+                           logprobs=None):                                                                    # :915-1126
         """``shard`` (``dist.KVShard``, every rank of the group calls with the same arguments): the prompt is prefilled
         and its KV kept sequence-sharded over the ranks (``_sharded_prefill``); decoding then runs replicated with one
         exchange per attention call.  Returns the same values on every rank.  ``sampling``: the verification pass draws
         one token per row and the greedy acceptance runs on the draws (not with a vocabulary-parallel shard).  ``penalties``:
         every verification row is penalised from its own history -- prompt, text so far and the tree path it follows (not with
-        a vocabulary-parallel shard; under a sequence shard every rank keeps the same state)."""
+        a vocabulary-parallel shard; under a sequence shard every rank keeps the same state).  ``logprobs``: the log-probs of
+        the emitted tokens and their top-n alternatives as ``self.last_logprobs`` (not with a vocabulary-parallel shard; under
+        a sequence shard every rank computes the same values)."""
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         pen = _resolve_penalties(penalties, temperature, use_env=True)
+        lpc = _resolve_logprobs(logprobs, temperature, use_env=True)
         if sampling is not None and shard is not None and shard.vocab_parallel:
             raise ValueError("sampling= is not available with a vocabulary-parallel shard")
         if pen is not None and shard is not None and shard.vocab_parallel:
             raise ValueError("penalties= is not available with a vocabulary-parallel shard")
+        if lpc is not None and shard is not None and shard.vocab_parallel:
+            raise ValueError("logprobs= is not available with a vocabulary-parallel shard")
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
         dev = input_ids.device
@@ -746,19 +807,22 @@ class LlamaGlide(LlamaForCausalLM):
                 # a mailbox slot holds the record of the widest pass: 128 rows x heads x (128 + 1) floats
                 heads = max(self.config.num_attention_heads, self.glide.config.num_attention_heads)
                 shard.enable_peer_exchange(bsz * 128 * heads * 129, dev)
-            first = self._sharded_prefill(input_ids, input_len, position_ids, shard, sampling, pen, pstate)
+            first, first_lp = self._sharded_prefill(input_ids, input_len, position_ids, shard, sampling, pen, pstate, lpc)
         else:
             # prefill LLM (:954-960)
             self._set_hints(P, P)
             hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
-            first = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), sampling, input_len, pen, pstate)
+            first, first_lp = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), sampling, input_len, pen,
+                                                pstate, lpc)
             # prefill glide (:968-975)
             hidden_states = self.model.embed_tokens(input_ids)
             position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=lens.clone(), llm_kv_len=lens.clone(), exec_type="prefill")
         st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature, sampling=sampling,
-                                    penalties=penalties, prompt_ids=input_ids, prompt_state=pstate)
+                                    penalties=penalties, prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs,
+                                    first_logprobs=first_lp)
+        self.last_logprobs = st.logprobs
         _sync(input_ids)
         start_time = time.time()
         for out_index in range(1, max_gen_len):
@@ -775,11 +839,12 @@ class LlamaGlide(LlamaForCausalLM):
             shard.raise_if_exchange_failed()
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
-    def _sharded_prefill(self, input_ids, input_len, position_ids, shard, sampling=None, penalties=None, prompt_state=None):
+    def _sharded_prefill(self, input_ids, input_len, position_ids, shard, sampling=None, penalties=None, prompt_state=None,
+                         logprobs=None):
         """Sequence-sharded prefill: rank r runs the target model on prompt rows [r*Ls, (r+1)*Ls) only
         (one all-gather of the layer's K/V rows per layer, ``LlamaAttention.sharded_prefill``) and keeps that slice of the
-        KV; the tail rank computes the first token and broadcasts it.  The draft layer's cache is filled on every rank
-        (its rows depend on the token ids only).  Work per rank: 1/W of the projections / MLP, between 1/W^2 (rank 0)
+        KV; the tail rank computes the first token (and, under ``logprobs``, its log-prob rows) and broadcasts it.  The
+        draft layer's cache is filled on every rank (its rows depend on the token ids only).  Work per rank: 1/W of the projections / MLP, between 1/W^2 (rank 0)
         and (2W-1)/W^2 (tail) of the attention."""
         bsz, P = input_ids.shape
         assert bsz == 1 and int(input_len.view(-1)[0]) == P, "sharded prefill: batch 1, unpadded prompt"
@@ -797,16 +862,27 @@ class LlamaGlide(LlamaForCausalLM):
                                                exec_type="prefill").last_hidden_state
         finally:
             shard.prefill_ctx = None
-        first = torch.zeros((bsz,), dtype=torch.int64, device=input_ids.device)
+        dev = input_ids.device
+        first = torch.zeros((bsz,), dtype=torch.int64, device=dev)
+        first_lp = None
+        if logprobs is not None:
+            first_lp = (torch.zeros((bsz, 1), dtype=torch.float32, device=dev),
+                        torch.zeros((bsz, 1, logprobs.top_n), dtype=torch.float32, device=dev),
+                        torch.zeros((bsz, 1, logprobs.top_n), dtype=torch.int64, device=dev))
         if shard.is_tail:
-            first = self._first_token(self.lm_head(hidden_states[:, hi - lo - 1, :]), sampling, input_len, penalties, prompt_state)
+            first, first_lp = self._first_token(self.lm_head(hidden_states[:, hi - lo - 1, :]), sampling, input_len, penalties,
+                                                prompt_state, logprobs)
         shard.broadcast_from_tail(first)
+        for t in first_lp or ():
+            if t.numel():
+                shard.broadcast_from_tail(t)
         hidden_states = self.model.embed_tokens(input_ids)
         self.glide.prefill_cache_only(hidden_states, self.model.rotary_emb(hidden_states, position_ids))
-        return first
+        return first, first_lp
 
     def begin_tree_decode(self, first_token, cache_lens, prompt_bound: int, tree_shape=None, max_gen_len=64, eos_id=151645,
-                          temperature=0.0, sampling=None, penalties=None, prompt_ids=None, prompt_state=None):
+                          temperature=0.0, sampling=None, penalties=None, prompt_ids=None, prompt_state=None, logprobs=None,
+                          first_logprobs=None):
         """State of the round loop right after the two prefills (``llama_glide.py:927-991``).
         ``first_token`` [bsz] = the target's first generated token, ``cache_lens`` [bsz] int32 = valid
         rows of every KV cache, ``prompt_bound`` = host-side bound of it.  Also the entry point of
@@ -815,10 +891,13 @@ class LlamaGlide(LlamaForCausalLM):
         the process-wide default LONGSPEC_SAMPLING, else greedy).  ``penalties``: the verification rows are penalised in front
         of that arg-max or draw, row j from ``st.token_state`` (``prompt_ids[z, :cache_lens[z]]``, None: no prompt flags, and
         the text so far) plus the tokens on node j's path (None at temperature 0: the process-wide default
-        LONGSPEC_PENALTIES, else none)."""
+        LONGSPEC_PENALTIES, else none).  ``logprobs``: the rows on the accepted path fill their columns of ``st.logprobs``
+        inside the round and its graph (None at temperature 0: the process-wide default LONGSPEC_LOGPROBS, else none;
+        ``first_logprobs``: the first token's rows, for column 0)."""
         dev = first_token.device
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         penalties = _resolve_penalties(penalties, temperature, use_env=True)
+        logprobs = _resolve_logprobs(logprobs, temperature, use_env=True)
         sh = self.model.layers[-1].self_attn.shard
         if sampling is not None and sh is not None and sh.vocab_parallel:
             raise ValueError("sampling= is not available with a vocabulary-parallel shard")
@@ -833,6 +912,7 @@ class LlamaGlide(LlamaForCausalLM):
         self._head_of_draft_passes()                    # the draft passes' head and its pack exist before the first warm-up round
         st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz, sampling=sampling)
         self._begin_penalties(st, penalties, bsz, dev, prompt_ids, cache_lens, first_token, prompt_state)
+        self._begin_logprobs(st, logprobs, bsz, max_gen_len, dev, first_logprobs)
         st.output_ids = torch.full((bsz, max_gen_len), self._tree_output_fill(eos_id), dtype=torch.int64, device=dev)  # :937 (G8)
         st.spec_mask = torch.zeros((bsz, max_gen_len), dtype=torch.int64, device=dev)
         st.output_ids[:, 0] = first_token
@@ -946,6 +1026,7 @@ class LlamaGlide(LlamaForCausalLM):
         st.graphs_forced = True
         names = ("cache_lens", "target_cache_lens_for_draft", "draft_cache_lens", "tree_mask", "all_spec", "history_logp_sum",
                  "acc_pad", "output_ids", "emitted_dev") + (("token_state",) if st.token_state is not None else ())
+        lp_bufs = (st.logprobs.token, st.logprobs.top_ids, st.logprobs.top) if st.logprobs is not None else ()
         with rp.guard():
             rp.roll_over(st.emitted)
             for a in range(1, st.gamma + 2):
@@ -954,9 +1035,12 @@ class LlamaGlide(LlamaForCausalLM):
                 device_round = partial(self._round_device, st, a)
                 if a not in rp.entries:
                     snap = {n: getattr(st, n).clone() for n in names}
+                    lp_snap = [t.clone() for t in lp_bufs]
                     rp.warm(a, device_round)
                     for n in names:
                         getattr(st, n).copy_(snap[n])
+                    for t, saved in zip(lp_bufs, lp_snap):
+                        t.copy_(saved)
                 rp.capture(a, device_round)
 
     def _round_device(self, st, a: int):
@@ -1052,8 +1136,14 @@ class LlamaGlide(LlamaForCausalLM):
             kv_lens, kc, vc = sh.local_len(st.cache_lens), last_attn.K_Cache, last_attn.V_Cache
         else:
             kv_lens, kc, vc = st.cache_lens, None, None
-        acc_pad, acc_num_t, double_input, _ = ops.tree_collapse(all_spec, all_llm_pred, tree_mask, kv_lens, acc_n[-2],
-                                                                gamma + 1, kc, vc, cache_len_add=a - 1, out_acc_ids=st.acc_pad)
+        acc_pad, acc_num_t, double_input, index_mapping = ops.tree_collapse(all_spec, all_llm_pred, tree_mask, kv_lens, acc_n[-2],
+                                                                            gamma + 1, kc, vc, cache_len_add=a - 1,
+                                                                            out_acc_ids=st.acc_pad)
+        if st.logprobs is not None:
+            # the accepted rows' log-probs -> the columns tree_commit is about to write, behind emitted_dev as it stands now
+            lp = st.logprobs
+            ops.logprob_commit(ops.token_logprobs(llm_logits, all_llm_pred, lp.temperature, lp.top_n), lp, st.emitted_dev,
+                               num=acc_num_t, index_map=index_mapping)
         # emitted tokens -> output_ids (at the device-side offset), the EOS test on the whole buffer as the reference
         # does (:1120, G8), the tree state reset and `cache_lens += a`, `target_cache_lens_for_draft += acc_num`
         # (:1104-1117): one launch; its result is the round's ONE host read for (acc_num, eos flag)

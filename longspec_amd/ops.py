@@ -15,6 +15,8 @@ One function per reference seam of the draft-then-verify round:
                          no counterpart in the reference)
   penalize_rows / token_state_add   repetition / presence / frequency penalties and a logit bias on the target's logits, per
                          row from that row's own history, and the [batch, vocab] state they read (penalties=; no counterpart)
+  token_logprobs / logprob_commit   log-prob of every emitted token under the distribution it was taken from and the row's
+                         top-n alternatives; the accepted rows' results -> the tokens' output columns (logprobs=; no counterpart)
   tree_commit / tree_commit_stochastic   end of a round at temperature 0 / > 0  llama_glide.py:1093-1121
   linear / linear_multi / mlp_gate_up   the projections of a decode pass (M <= 80 token rows):
                          q/k/v/o_proj llama.py:361-363,390, LlamaMLP (qwen2.py:218-230), lm_head llama_glide.py:1091
@@ -104,7 +106,8 @@ _gemm_ws = _ZeroedWorkspace()
 
 def workspace_tensors():
     """The scratch buffers currently handed out (a captured HIP graph keeps them alive: it holds their addresses)."""
-    return list(_ws._buf.values()) + list(_gemm_ws._buf.values()) + list(_sample_ws._buf.values())
+    return (list(_ws._buf.values()) + list(_gemm_ws._buf.values()) + list(_sample_ws._buf.values())
+            + list(_logprob_ws._buf.values()))
 
 
 _linear_need = {}            # (shape key) -> workspace bytes of the launch plan
@@ -469,6 +472,78 @@ def token_state_add(state: torch.Tensor, ids: torch.Tensor, num: Optional[torch.
         num_p, num_s = num.data_ptr(), num.stride(0)
     _C.check(_C.load().ls_token_state_add(state.data_ptr(), b, V, state.stride(0), ids.data_ptr(), ids.shape[1], ids.stride(0),
                                           num_p, num_s, 1 if prompt else 0, _stream()), "ls_token_state_add")
+
+
+_logprob_ws = _Workspace()   # its own buffer, as _sample_ws: a captured round holds its address
+LOGPROB_MAX_ROWS, LOGPROB_MAX_N = 1024, 20      # the limits of ls_token_logprobs (rows x batch, top n)
+
+
+def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, temperature: float = 1.0, n: int = 0):
+    """Log-prob of the chosen token of every row of TARGET logits [b, V] or [b, R, V] -- as the token was picked from them,
+    i.e. behind ``penalize_rows`` -- and the row's top ``n`` (``ls_token_logprobs``): ``ids`` int64 [b] / [b, R].  In fp32,
+    ``lp_j = (x_j - m) / temperature - ln sum_i exp((x_i - m) / temperature)`` over the full vocabulary.  Returns
+    (row_lp [b, R] fp32, top_val [b, R, n] fp32, top_idx [b, R, n] int64): the n largest logits in (logit descending, column
+    ascending) order; an id outside the vocabulary gives NaN, a short row is padded with (-inf, -1)."""
+    _dev(logits, ids)
+    if logits.dim() not in (2, 3):
+        raise ValueError("token_logprobs: logits [b, V] or [b, R, V]")
+    x = logits if logits.dim() == 3 else logits.unsqueeze(1)
+    b, R, V = x.shape
+    if x.stride(2) != 1 or x.stride(0) % 8 != 0 or x.stride(1) % 8 != 0 or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    if ids.dtype != torch.int64 or ids.numel() != b * R or ids.shape[0] != b:
+        raise TypeError(f"token_logprobs: ids must be int64 [{b}, {R}]")
+    ids = ids.view(b, R)
+    if R > 1 and ids.stride(1) != 1:
+        ids = ids.contiguous()
+    dev = x.device
+    row_lp = torch.empty((b, R), dtype=torch.float32, device=dev)
+    top_val = torch.empty((b, R, n), dtype=torch.float32, device=dev)
+    top_idx = torch.empty((b, R, n), dtype=torch.int64, device=dev)
+    lib = _C.load()
+    # sized once for the largest call the kernel takes at this vocabulary (3.3 MB at V = 128 256), not for this call: the
+    # buffer of a stream never moves while the vocabulary stays, so a captured round's address stays the one later calls use
+    need = lib.ls_token_logprobs_workspace_bytes(1, LOGPROB_MAX_ROWS, V, LOGPROB_MAX_N)
+    ws = _logprob_ws.get(dev, max(need, 1))
+    _C.check(lib.ls_token_logprobs(x.data_ptr(), b, R, V, _dtype(x), x.stride(0), x.stride(1), ids.data_ptr(), ids.stride(0),
+                                   float(temperature), n, row_lp.data_ptr(), top_val.data_ptr() if n else None,
+                                   top_idx.data_ptr() if n else None, ws.data_ptr(), ws.numel(), _stream()), "ls_token_logprobs")
+    return row_lp, top_val, top_idx
+
+
+def logprob_commit(rows, out, base: torch.Tensor, base_add: int = 0, num: Optional[torch.Tensor] = None,
+                   index_map: Optional[torch.Tensor] = None) -> None:
+    """The accepted rows of ``rows`` = (row_lp, top_val, top_idx) of ``token_logprobs`` -> the columns of ``out`` (a namespace
+    of ``token`` [b, W] fp32, ``top`` [b, W, n] fp32, ``top_ids`` [b, W, n] int64, dense) that belong to the tokens they
+    produced (``ls_logprob_commit``, one launch): for ``j < num[z]`` (int64 [b], any stride; None: every row of ``index_map``,
+    or of ``rows``), row ``index_map[z, j]`` (int64 [b, J]; None: row j) goes to column ``base[z] + base_add + j`` (``base``
+    int32 [b]).  Rows and columns out of range are skipped."""
+    row_lp, top_val, top_idx = rows
+    _dev(row_lp, top_val, top_idx, out.token, out.top, out.top_ids, base, num, index_map)
+    b, R = row_lp.shape
+    n = top_val.shape[2]
+    W = out.token.shape[1]
+    for t, shape, dt, name in ((row_lp, (b, R), torch.float32, "row_lp"), (top_val, (b, R, n), torch.float32, "top_val"),
+                               (top_idx, (b, R, n), torch.int64, "top_idx"), (out.token, (b, W), torch.float32, "out.token"),
+                               (out.top, (b, W, n), torch.float32, "out.top"), (out.top_ids, (b, W, n), torch.int64, "out.top_ids")):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise TypeError(f"logprob_commit: {name} must be a contiguous {dt} tensor of shape {shape}")
+    if base.dtype != torch.int32 or base.numel() != b or not base.is_contiguous():
+        raise TypeError("logprob_commit: base must be a contiguous int32 [b] tensor")
+    J, map_p = R, None
+    if index_map is not None:
+        if index_map.dtype != torch.int64 or index_map.dim() != 2 or index_map.shape[0] != b or not index_map.is_contiguous():
+            raise TypeError("logprob_commit: index_map must be a contiguous int64 [b, J] tensor")
+        J, map_p = index_map.shape[1], index_map.data_ptr()
+    num_p, num_s = None, 0
+    if num is not None:
+        if num.dtype != torch.int64 or num.numel() != b or num.dim() != 1:
+            raise TypeError("logprob_commit: num must be int64 [b]")
+        num_p, num_s = num.data_ptr(), num.stride(0)
+    ptr = lambda t: t.data_ptr() if n else None
+    _C.check(_C.load().ls_logprob_commit(row_lp.data_ptr(), ptr(top_val), ptr(top_idx), b, R, n, map_p, J, num_p, num_s,
+                                         base.data_ptr(), base_add, out.token.data_ptr(), ptr(out.top), ptr(out.top_ids), W,
+                                         _stream()), "ls_logprob_commit")
 
 
 TOPK_CHUNK = 8192          # logits per stage-1 record (ls_topk_chunk(); checked at first use)
@@ -1140,6 +1215,13 @@ def rope_apply_(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.
     for t in (q, k):
         if t.stride(-1) != 1 or t.stride(2) != 128 or (b > 1 and t.stride(0) != R * t.stride(1)):
             raise ValueError("rope_apply_: heads must be packed (stride 128) and rows uniformly strided")
+    # the kernel reads one cos / sin row per (batch, position) row: a table of one batch row -- a batched prefill, whose
+    # position_ids are [1, R] -- is broadcast over the batch as apply_rotary_pos_emb does, never read past its end
+    if cos.shape != sin.shape or cos.dtype != q.dtype or sin.dtype != q.dtype or cos.numel() not in (R * 128, b * R * 128):
+        raise ValueError(f"rope_apply_: cos / sin must be [1 or {b}, {R}, 128] tables of q's dtype, got {tuple(cos.shape)}")
+    if cos.numel() != b * R * 128:
+        cos, sin = cos.reshape(1, R, 128).expand(b, R, 128), sin.reshape(1, R, 128).expand(b, R, 128)
+    cos, sin = cos.contiguous(), sin.contiguous()
     lib = _C.load()
     _C.check(lib.ls_rope_apply(q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), b * R, Hq, Hk, q.stride(1),
                                k.stride(1), _dtype(q), _stream()), "ls_rope_apply")
