@@ -417,6 +417,36 @@ int ls_logprob_commit(const float* row_lp, const float* row_top_val, const int64
                       const int64_t* map, int max_rows, const int64_t* num, int64_t num_stride, const int32_t* base, int base_add,
                       float* out_token, float* out_top_val, int64_t* out_top_idx, int out_cap, void* stream);
 
+/* Stop conditions of the decode loops (stop=; csrc/stop.hip; no counterpart in the reference, which tests one EOS id).
+ * table: int32 [LS_STOP_TABLE_WORDS] on the device -- [0] n_ids (0..64), [1] n_seqs (0..16), [2] min_tokens, [3] the word count,
+ * [4:68] the stop token ids (-1 padded), [68:85] offsets of the stop sequences into the token area, [85:341] their tokens back to
+ * back (1..16 each).  Counts and offsets are clamped to this layout on the device before they index anything.
+ *
+ * ls_stop_scan: one wave per batch row, behind the round's commit.  output_ids [b, width] int64 (row stride out_stride_b);
+ * w = written[z] - (written_sub ? written_sub[z] : 0) + written_add columns are written (clamped to 0..width), the last
+ * n = (num ? num[z * num_stride] : num_const) of them by this round (clamped to 0..w).  A stop matches at column c >= min_tokens
+ * when output_ids[z, c] is a stop id, or a sequence of length L <= c + 1 equals output_ids[z, c-L+1 : c+1]; no read goes in front
+ * of column 0 or to column w and beyond.  Among the round's columns the smallest c wins and, there, the first stop in listing
+ * order (ids, then sequences): stop_state[z] (int32 [b, 4]) = (length = c + 1, which, match_start = c - L + 1, reserved).  A row
+ * whose stop_state[z, 0] is >= 0 already matches nothing new.  In both cases the columns [length, w) of output_ids go back to
+ * `fill`, of spec_mask (optional, row stride mask_stride_b) to 0, of lp_token / lp_top / lp_top_ids (optional, dense
+ * [b, width(, lp_n)]) to NaN / -inf / -1, and round_state[z * state_stride_b + 1] |= 2 (optional: the round's state tensor, so that
+ * its one host read carries the hit).  A row without a match is not touched.  Exact; no workspace, no atomics.
+ *
+ * ls_stop_ban_rows: the min_tokens ban on 16-bit target logits [b, rows, vocab] (strides in elements), IN PLACE, one wave per row.
+ * Row r of batch z predicts column (base ? base[z] : 0) - (base_sub ? base_sub[z] : 0) + base_add + depth(r), depth = 0
+ * (depth_mode 0), r (1) or the number of non-zero mask[z, r, 1 : mask_cols] (2; mask int64, batch / row strides, unit column
+ * stride).  Where that column is < min_tokens the entries of the stop ids inside [0, vocab) become -inf; every other element and
+ * every other row keeps its bits. */
+#define LS_STOP_TABLE_WORDS 341
+int ls_stop_scan(int64_t* output_ids, int b, int64_t out_stride_b, int width, const int32_t* written, const int32_t* written_sub,
+                 int written_add, const int64_t* num, int64_t num_stride, int num_const, const int32_t* table, int table_words,
+                 int32_t* stop_state, int64_t fill, int64_t* round_state, int64_t state_stride_b, int64_t* spec_mask,
+                 int64_t mask_stride_b, float* lp_token, float* lp_top, int64_t* lp_top_ids, int lp_n, void* stream);
+int ls_stop_ban_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t stride_b, int64_t stride_r, const int32_t* table,
+                     int table_words, const int32_t* base, const int32_t* base_sub, int base_add, int depth_mode,
+                     const int64_t* mask, int64_t mask_stride_b, int64_t mask_stride_r, int mask_cols, void* stream);
+
 /* ls_logprob_topk and ls_argmax_rows with the lm_head SHARDED BY VOCABULARY over the ranks of a node (no counterpart in the reference, which
  * replicates: llama_glide.py:474).  A "record" is what stage 1 produces per (8192-logit chunk, row): the chunk's max, its sum of
  * exp(x - max) and its k largest logits with their GLOBAL columns -- rows * (2 + 2k) floats per chunk slot, chunk-major.

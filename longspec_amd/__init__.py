@@ -9,3 +9,4 @@ __version__ = "0.1.0"
 from .sampling import Sampling  # noqa: E402,F401
 from .penalties import Penalties  # noqa: E402,F401
 from .logprobs import Logprobs  # noqa: E402,F401
+from .stop import Stop  # noqa: E402,F401

@@ -25,6 +25,7 @@ from .graphs import GraphReplayer
 from .sampling import resolve as _resolve_sampling
 from .penalties import resolve as _resolve_penalties
 from .logprobs import new_buffers as _logprob_buffers, resolve as _resolve_logprobs
+from .stop import new_state as _stop_state, resolve as _resolve_stop, result_of as _stop_result
 from .llama import (DecodeLinear, LlamaForCausalLM, LlamaMLP, LlamaRMSNorm, chunked_causal_prefill,
                     project_qkv, _default_ops)
 
@@ -401,12 +402,40 @@ class LlamaGlide(LlamaForCausalLM):
             lp.token[:, 0], lp.top[:, 0], lp.top_ids[:, 0] = first[0][:, 0], first[1][:, 0], first[2][:, 0]
         st.logprobs = lp
 
-    def _first_token(self, logits, sampling, input_len, penalties=None, prompt_state=None, logprobs=None):
+    def _begin_stop(self, st, stop, bsz: int, device, table=None):
+        """The stop part of a decode state: ``st.stop`` = None, or a namespace of ``cfg`` (the ``Stop``), ``table`` (its int32
+        device table, ``table`` when the caller has built it already, for the first token) and ``min_tokens``;
+        ``st.stop_state`` [bsz, 4] int32 = (length, which, match_start, reserved), -1 while nothing has stopped;
+        ``st.last_stop`` = the namespace the loops publish (views of it); ``st.stopped`` = the host's copy of "a round reported
+        a stop".  ``min_tokens > 0`` is refused under a vocabulary-parallel shard: no rank holds a whole row of logits there."""
+        st.stop, st.stop_state, st.last_stop, st.stopped = None, None, None, False
+        if stop is None:
+            return
+        sh = self.model.layers[-1].self_attn.shard
+        if stop.min_tokens > 0 and sh is not None and sh.vocab_parallel:
+            raise ValueError("stop= with min_tokens > 0 is not available with a vocabulary-parallel shard")
+        if table is None:
+            table = stop.table(self.lm_head.out_features, device)
+        st.stop = SimpleNamespace(cfg=stop, table=table, min_tokens=stop.min_tokens)
+        st.stop_state = _stop_state(bsz, device)
+        st.last_stop = _stop_result(st.stop_state)
+
+    def _stop_scan(self, st, written, written_sub=None, written_add=0, num=None, fill=0, state=None):
+        """``ops.stop_scan`` on a decode state: the columns this round (``num`` per row; None: one) wrote to ``st.output_ids``,
+        erasing ``st.spec_mask`` and ``st.logprobs`` along with it where the state has them."""
+        self.ops.stop_scan(st.output_ids, st.stop.table, st.stop_state, written, written_sub=written_sub, written_add=written_add,
+                           num=num, fill=fill, state=state, spec_mask=getattr(st, "spec_mask", None), logprobs=st.logprobs)
+
+    def _first_token(self, logits, sampling, input_len, penalties=None, prompt_state=None, logprobs=None, stop=None,
+                     stop_table=None):
         """The prefill's token from ``logits`` [bsz, V] of prompt row ``input_len - 1``; under ``penalties`` the history of
-        that row is the prompt alone (``prompt_state``: ``_token_state`` of the prompt).  Returns (token, its log-prob rows
+        that row is the prompt alone (``prompt_state``: ``_token_state`` of the prompt); under a ``stop`` with ``min_tokens > 0``
+        the stop ids of ``stop_table`` are banned from it (column 0).  Returns (token, its log-prob rows
         (``ops.token_logprobs``) under ``logprobs``, else None)."""
         if penalties is not None:
             logits = self.ops.penalize_rows(logits, prompt_state, penalties)
+        if stop is not None and stop.min_tokens > 0:
+            logits = self.ops.stop_ban_rows(logits, stop_table)
         if sampling is None:
             token = logits.argmax(dim=-1)
         else:
@@ -439,17 +468,24 @@ class LlamaGlide(LlamaForCausalLM):
 
     @torch.inference_mode()
     def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645, sampling=None,
-                         penalties=None, logprobs=None):                                                           # :552-585
+                         penalties=None, logprobs=None, stop=None):                                                # :552-585
         """``sampling`` (``longspec_amd.Sampling``): every token is drawn from the target's filtered distribution instead of
         taken as its arg-max -- the denominator of a sampled speculative run, and with the same seed the same text.
         ``penalties`` (``longspec_amd.Penalties``): the logits of every step are penalised from the prompt and the text so far.
         ``logprobs`` (``longspec_amd.Logprobs``): the log-prob of every token under the distribution it was taken from and its
         top-n alternatives, published as ``self.last_logprobs`` (``logprobs.py``; None without it); the return tuple is
-        unchanged."""
+        unchanged.
+        ``stop`` (``longspec_amd.Stop``): a row ends at its first stop match (``stop.py``): its columns behind the match go
+        back to 0, the loop ends when every row has stopped (tested where the EOS test is, every 16th step) and the elapsed
+        time is cut back to the step of the last row's stop.  The result is ``self.last_stop`` (None without it).  The built-in
+        EOS test runs alongside, unchanged.  ``num``, the KV lengths and the penalty state are not rolled back: they describe
+        the steps that ran, ``last_stop.length`` is the authority on the text."""
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, None, use_env=True)
         pen = _resolve_penalties(penalties, None, use_env=True)
         lpc = _resolve_logprobs(logprobs, None, use_env=True)
+        stp = _resolve_stop(stop, None, use_env=True)
+        stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
         self._clear_shard()
         bsz = input_ids.size(0)
         output_ids = input_ids.new_zeros((bsz, max_gen_len))
@@ -462,7 +498,7 @@ class LlamaGlide(LlamaForCausalLM):
         rows = torch.arange(bsz, device=input_ids.device)
         pstate = self._token_state(bsz, input_ids.device, input_ids, input_len) if pen is not None else None
         output_ids[:, 0], first_lp = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), sampling, input_len,
-                                                       pen, pstate, lpc)
+                                                       pen, pstate, lpc, stp, stab)
         cache_lens += input_len.int()
         num = 0
         eos = self._stop_id(eos_id, "vanilla")
@@ -474,8 +510,10 @@ class LlamaGlide(LlamaForCausalLM):
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record()
         vs = self.begin_vanilla_decode(output_ids, cache_lens, input_len.int(), P, sampling=sampling, penalties=penalties,
-                                       prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp)
+                                       prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp,
+                                       stop=stop, stop_table=stab)
         self.last_logprobs = vs.logprobs
+        self.last_stop = vs.last_stop
         for step in range(1, max_gen_len):
             self.vanilla_step(vs)
             num += bsz
@@ -487,7 +525,12 @@ class LlamaGlide(LlamaForCausalLM):
                 marks.append(time.time() - start_time)
             # the reference reads the EOS test back after every token (:578); here every 16th, and the result is then cut
             # back to what the reference would have returned -- tokens, `num` AND elapsed time
-            if eos is not None and (step % 16 == 0 or step == max_gen_len - 1):
+            if vs.stop is not None and (step % 16 == 0 or step == max_gen_len - 1):
+                # the same poll, still ONE host read: (EOS anywhere, every row has stopped)
+                hit = output_ids[:, :step + 1].eq(eos).any() if eos is not None else vs.stop_state.new_zeros((), dtype=torch.bool)
+                if any(torch.stack([hit, vs.stop_state[:, 0].ge(0).all()]).tolist()):
+                    break
+            elif eos is not None and (step % 16 == 0 or step == max_gen_len - 1):
                 if bool((output_ids[:, :step + 1].eq(eos)).any()):
                     break
         _sync(input_ids)
@@ -499,26 +542,41 @@ class LlamaGlide(LlamaForCausalLM):
                 lp.token[:, stop + 1:], lp.top_ids[:, stop + 1:], lp.top[:, stop + 1:] = float("nan"), -1, float("-inf")
             if stop is not None and stop < len(marks):
                 elapsed_time = ev0.elapsed_time(marks[stop - 1]) * 1e-3 if on_gpu else marks[stop - 1]
+                marks = marks[:stop]
+        if vs.stop is not None:
+            lengths = vs.stop_state[:, 0].tolist()
+            if min(lengths) >= 0:                                     # every row stopped: step s wrote column s
+                last = max(max(lengths) - 1, 1)
+                if last < len(marks):
+                    elapsed_time = ev0.elapsed_time(marks[last - 1]) * 1e-3 if on_gpu else marks[last - 1]
         return output_ids, num, elapsed_time
 
     # ------------------------------------------------------------------------------------------
     def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int, sampling=None, penalties=None,
-                             prompt_ids=None, prompt_state=None, logprobs=None, first_logprobs=None):
+                             prompt_ids=None, prompt_state=None, logprobs=None, first_logprobs=None, stop=None, stop_table=None):
         """State of the vanilla loop (``llama_glide.py:566-583``): ``output_ids`` [bsz, max_gen] with the first
         token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32.  ``sampling``:
         draw instead of arg-max (None: the process-wide default LONGSPEC_SAMPLING, else greedy).  ``penalties``: penalise
         every step's logits (None: the process-wide default LONGSPEC_PENALTIES, else none) from ``vs.token_state``, which
         starts from ``prompt_ids[z, :input_len[z]]`` (None: no prompt flags; ``prompt_state``: those flags, already built)
         and the first token.  ``logprobs``: every step also fills its column of ``vs.logprobs`` (None: the process-wide
-        default LONGSPEC_LOGPROBS, else none; ``first_logprobs``: the first token's rows, for column 0)."""
+        default LONGSPEC_LOGPROBS, else none; ``first_logprobs``: the first token's rows, for column 0).  ``stop``: every step
+        tests its column against the stops (``stop.py``; None: the process-wide default LONGSPEC_STOP, else none;
+        ``stop_table``: its device table, already built) and keeps ``vs.stop_state`` / ``vs.last_stop``; column 0 is tested
+        here.  A row that has stopped keeps decoding with the batch, and every step erases what it wrote; KV lengths and the
+        penalty state are not rolled back."""
         dev = output_ids.device
         sampling = _resolve_sampling(sampling, None, use_env=True)
         penalties = _resolve_penalties(penalties, None, use_env=True)
         logprobs = _resolve_logprobs(logprobs, None, use_env=True)
+        stop = _resolve_stop(stop, None, use_env=True)
         vs = _DecodeState(output_ids=output_ids, cache_lens=cache_lens, input_len=input_len, P=prompt_bound, step=0,
                           rows=torch.arange(output_ids.size(0), device=dev), sampling=sampling, penalties=penalties)
         self._begin_penalties(vs, penalties, output_ids.size(0), dev, prompt_ids, input_len, output_ids[:, 0], prompt_state)
         self._begin_logprobs(vs, logprobs, output_ids.size(0), output_ids.size(1), dev, first_logprobs)
+        self._begin_stop(vs, stop, output_ids.size(0), dev, stop_table)
+        if vs.stop is not None:
+            self._stop_scan(vs, cache_lens, input_len, 1)
         vs.streams = torch.arange(output_ids.size(0), device=dev, dtype=torch.int32) if sampling is not None else None
         vs.use_graphs = bool(dev.type == "cuda" and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
         P = prompt_bound                                   # (the replayer holds no reference to the state that holds it)
@@ -534,6 +592,8 @@ class LlamaGlide(LlamaForCausalLM):
         logits = self.lm_head(hidden_states[:, -1, :])
         if vs.penalties is not None:
             logits = self.ops.penalize_rows(logits, vs.token_state, vs.penalties, bias=vs.bias_table)
+        if vs.stop is not None and vs.stop.min_tokens > 0:    # the row predicts column cl - il + 1
+            logits = self.ops.stop_ban_rows(logits, vs.stop.table, base=cl, base_sub=il, base_add=1)
         llm_output = self._target_tokens(logits, vs.sampling, cl, vs.streams)
         cl += 1
         out[rows, (cl - il).long()] = llm_output.view(-1)
@@ -543,6 +603,8 @@ class LlamaGlide(LlamaForCausalLM):
                                     (cl - il).to(torch.int32))
         if vs.penalties is not None:
             self.ops.token_state_add(vs.token_state, llm_output.view(out.size(0), 1))
+        if vs.stop is not None:
+            self._stop_scan(vs, cl, il, 1)
 
     def vanilla_step(self, vs):
         """Decode one token.  On a GPU the step is captured into a HIP graph after GRAPH_AFTER eager steps and replayed."""
@@ -568,18 +630,18 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def spec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                      sampling=None, penalties=None, logprobs=None):                                               # :621-774
+                      sampling=None, penalties=None, logprobs=None, stop=None):                                    # :621-774
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="glide",
-                                    sampling=sampling, penalties=penalties, logprobs=logprobs)
+                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop)
 
     @torch.inference_mode()
     def magicdec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                          sampling=None, penalties=None, logprobs=None):                                           # :776-913
+                          sampling=None, penalties=None, logprobs=None, stop=None):                                # :776-913
         """The MagicDec baseline of the reference's harness (``--method magicdec``): chain speculation where the
         drafter is the TARGET itself attending to a StreamingLLM cache (32 sink rows + the last 1024 prompt rows +
         what it generates), verified exactly like ``spec_generate``.  Same return tuple."""
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="magicdec",
-                                    sampling=sampling, penalties=penalties, logprobs=logprobs)
+                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop)
 
     @torch.inference_mode()
     def vanilla_torch_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645):                      # :587-619
@@ -590,11 +652,13 @@ class LlamaGlide(LlamaForCausalLM):
         return self.vanilla_generate(input_ids, prompt_length, max_gen_len=max_gen_len, eos_id=eos_id)
 
     def _chain_generate(self, input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter, sampling=None,
-                        penalties=None, logprobs=None):
+                        penalties=None, logprobs=None, stop=None):
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         pen = _resolve_penalties(penalties, temperature, use_env=True)
         lpc = _resolve_logprobs(logprobs, temperature, use_env=True)
+        stp = _resolve_stop(stop, temperature, use_env=True)
+        stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
         magic = drafter == "magicdec"       # (temperature > 0: the same rejection block in both loops, :715-736 = :854-875)
         self._clear_shard()
         bsz = input_ids.size(0)
@@ -617,11 +681,12 @@ class LlamaGlide(LlamaForCausalLM):
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=cache_lens.clone(), llm_kv_len=cache_lens.clone(), exec_type="prefill")
         pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
-        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc)
+        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab)
         st = self.begin_chain_decode(first, cache_lens, input_len, P, gamma, max_gen_len, eos_id, temperature, drafter,
                                      first_logits=logits, sampling=sampling, penalties=penalties, prompt_ids=input_ids,
-                                     prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp)
+                                     prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp, stop=stop, stop_table=stab)
         self.last_logprobs = st.logprobs
+        self.last_stop = st.last_stop
         _sync(input_ids)
         start_time = time.time()
         for out_index in range(1, max_gen_len):
@@ -633,7 +698,7 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_chain_decode(self, first_token, cache_lens, input_len, prompt_bound: int, gamma=4, max_gen_len=64, eos_id=151645,
                            temperature=0.0, drafter="glide", first_logits=None, sampling=None, penalties=None, prompt_ids=None,
-                           prompt_state=None, logprobs=None, first_logprobs=None):
+                           prompt_state=None, logprobs=None, first_logprobs=None, stop=None, stop_table=None):
         """State of the chain-speculation loop right after the prefills (``llama_glide.py:641-668``): ``first_token`` [bsz]
         = the target's first generated token, ``cache_lens`` [bsz] int32 = valid rows of every cache (the draft's included),
         ``input_len`` [bsz] = prompt length, ``prompt_bound`` = host-side bound of it.  Also the entry point of benchmarks
@@ -642,12 +707,18 @@ class LlamaGlide(LlamaForCausalLM):
         the drafter stays greedy.  ``penalties``: the verification rows are penalised, row i from ``st.token_state`` (the prompt
         ``prompt_ids[z, :input_len[z]]``, None: no prompt flags, and the text so far) plus the i draft tokens it follows; the
         drafter stays unpenalised.  ``logprobs``: the rows a round accepts fill their columns of ``st.logprobs`` (None at
-        temperature 0: the process-wide default LONGSPEC_LOGPROBS, else none; ``first_logprobs``: the first token's rows)."""
+        temperature 0: the process-wide default LONGSPEC_LOGPROBS, else none; ``first_logprobs``: the first token's rows).
+        ``stop``: every round tests the columns it wrote against the stops (``stop.py``; None at temperature 0: the process-wide
+        default LONGSPEC_STOP, else none; ``stop_table``: its device table, already built) inside the round, in front of its one
+        host read; a match ends the loop with that round, the columns of ``output_ids`` / ``spec_mask`` / ``st.logprobs`` behind
+        it go back to their fill and ``st.last_stop`` holds (length, which, match_start).  KV lengths, ``st.token_state`` and the
+        host counters ``count`` / ``num`` / ``emitted`` are not rolled back: a stopped state is final."""
         bsz = first_token.size(0)
         dev = first_token.device
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         penalties = _resolve_penalties(penalties, temperature, use_env=True)
         logprobs = _resolve_logprobs(logprobs, temperature, use_env=True)
+        stop = _resolve_stop(stop, temperature, use_env=True)
         if drafter != "magicdec":
             self._head_of_draft_passes()                # the draft passes' head and its pack exist before the first round
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
@@ -678,11 +749,17 @@ class LlamaGlide(LlamaForCausalLM):
         st.next_spec_start_token[:, 0] = st.output_ids[:, 0]
         st.eos = self._stop_id(eos_id, "spec")
         st.stream_rows = self.model.layers[0].self_attn.STREAM_SINK + self.model.layers[0].self_attn.STREAM_WINDOW
+        self._begin_stop(st, stop, bsz, dev, stop_table)
+        if st.stop is not None:                              # column 0; a hit ends the loop with its first round
+            self._stop_scan(st, st.cache_lens, st.input_len_i32, 1)
         return st
 
     def chain_round(self, st) -> bool:
         """One round of ``spec_generate`` / ``magicdec_generate`` (``llama_glide.py:670-770``): gamma draft steps, one
-        (gamma + 1)-row target pass, acceptance by cumulative match.  False = stop (EOS or the buffer is full)."""
+        (gamma + 1)-row target pass, acceptance by cumulative match.  False = stop (EOS, a ``stop=`` match or the buffer is
+        full); on a state a ``stop=`` match has ended, False at once."""
+        if st.stopped:
+            return False
         gamma, magic, bsz, P = st.gamma, st.magic, st.bsz, st.P
         dev = st.output_ids.device
         output_ids, cache_lens, draft_cache_lens = st.output_ids, st.cache_lens, st.draft_cache_lens
@@ -734,6 +811,9 @@ class LlamaGlide(LlamaForCausalLM):
         if st.penalties is not None:
             llm_verify_logits = self.ops.penalize_rows(llm_verify_logits, st.token_state, st.penalties, spec_buffer[:, 1:],
                                                        st.chain_mask, bias=st.bias_table)
+        if st.stop is not None and st.stop.min_tokens > 0:   # row i predicts column cache_lens - input_len + 1 + i
+            llm_verify_logits = self.ops.stop_ban_rows(llm_verify_logits, st.stop.table, base=cache_lens, base_sub=st.input_len_i32,
+                                                       base_add=1, depth="row")
         # (sampling: verification row i was rotated to position cache_lens + i, models' forward :571-577)
         llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
                                                 cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
@@ -755,8 +835,11 @@ class LlamaGlide(LlamaForCausalLM):
             self.ops.token_state_add(st.token_state, llm_verify_output, num=state[:, 0])
         if lp_rows is not None:                              # ... and their log-probs, to the columns chain_commit wrote
             self.ops.logprob_commit(lp_rows, st.logprobs, lp_base, base_add=1, num=state[:, 0])
+        if st.stop is not None:                              # the stop test on those columns; a hit rides in state[:, 1] (bit 1)
+            self._stop_scan(st, cache_lens, st.input_len_i32, 1, num=state[:, 0], state=state)
         state = state.tolist()
         n_ok, hit = state[0][0], any(row[1] for row in state)
+        st.stopped = any(row[1] & 2 for row in state)
         st.double_flag = n_ok == gamma + 1
         st.count += n_ok - 1
         st.num += bsz
@@ -769,7 +852,7 @@ class LlamaGlide(LlamaForCausalLM):
     @torch.inference_mode()
     def tree_spec_generate(self, input_ids, prompt_length, tree_shape: Optional[List[int]] = None, max_gen_len=64,
                            eos_id=151645, temperature=0.0, shard=None, sampling=None, penalties=None,
-                           logprobs=None):                                                                    # :915-1126
+                           logprobs=None, stop=None):                                                         # :915-1126
         """``shard`` (``dist.KVShard``, every rank of the group calls with the same arguments): the prompt is prefilled
         and its KV kept sequence-sharded over the ranks (``_sharded_prefill``); decoding then runs replicated with one
         exchange per attention call.  Returns the same values on every rank.  ``sampling``: the verification pass draws
@@ -777,11 +860,17 @@ class LlamaGlide(LlamaForCausalLM):
         every verification row is penalised from its own history -- prompt, text so far and the tree path it follows (not with
         a vocabulary-parallel shard; under a sequence shard every rank keeps the same state).  ``logprobs``: the log-probs of
         the emitted tokens and their top-n alternatives as ``self.last_logprobs`` (not with a vocabulary-parallel shard; under
-        a sequence shard every rank computes the same values)."""
+        a sequence shard every rank computes the same values).  ``stop``: stop tokens, stop sequences and ``min_tokens``
+        (``stop.py``), the result as ``self.last_stop``; the stop test reads ``output_ids`` only, so every rank of either shard
+        computes the same result -- ``min_tokens > 0`` alone is refused with a vocabulary-parallel shard."""
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         pen = _resolve_penalties(penalties, temperature, use_env=True)
         lpc = _resolve_logprobs(logprobs, temperature, use_env=True)
+        stp = _resolve_stop(stop, temperature, use_env=True)
+        if stp is not None and stp.min_tokens > 0 and shard is not None and shard.vocab_parallel:
+            raise ValueError("stop= with min_tokens > 0 is not available with a vocabulary-parallel shard")
+        stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
         if sampling is not None and shard is not None and shard.vocab_parallel:
             raise ValueError("sampling= is not available with a vocabulary-parallel shard")
         if pen is not None and shard is not None and shard.vocab_parallel:
@@ -807,13 +896,14 @@ class LlamaGlide(LlamaForCausalLM):
                 # a mailbox slot holds the record of the widest pass: 128 rows x heads x (128 + 1) floats
                 heads = max(self.config.num_attention_heads, self.glide.config.num_attention_heads)
                 shard.enable_peer_exchange(bsz * 128 * heads * 129, dev)
-            first, first_lp = self._sharded_prefill(input_ids, input_len, position_ids, shard, sampling, pen, pstate, lpc)
+            first, first_lp = self._sharded_prefill(input_ids, input_len, position_ids, shard, sampling, pen, pstate, lpc, stp,
+                                                    stab)
         else:
             # prefill LLM (:954-960)
             self._set_hints(P, P)
             hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
             first, first_lp = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), sampling, input_len, pen,
-                                                pstate, lpc)
+                                                pstate, lpc, stp, stab)
             # prefill glide (:968-975)
             hidden_states = self.model.embed_tokens(input_ids)
             position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
@@ -821,8 +911,9 @@ class LlamaGlide(LlamaForCausalLM):
                        cache_lens=lens.clone(), llm_kv_len=lens.clone(), exec_type="prefill")
         st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature, sampling=sampling,
                                     penalties=penalties, prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs,
-                                    first_logprobs=first_lp)
+                                    first_logprobs=first_lp, stop=stop, stop_table=stab)
         self.last_logprobs = st.logprobs
+        self.last_stop = st.last_stop
         _sync(input_ids)
         start_time = time.time()
         for out_index in range(1, max_gen_len):
@@ -840,7 +931,7 @@ class LlamaGlide(LlamaForCausalLM):
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
     def _sharded_prefill(self, input_ids, input_len, position_ids, shard, sampling=None, penalties=None, prompt_state=None,
-                         logprobs=None):
+                         logprobs=None, stop=None, stop_table=None):
         """Sequence-sharded prefill: rank r runs the target model on prompt rows [r*Ls, (r+1)*Ls) only
         (one all-gather of the layer's K/V rows per layer, ``LlamaAttention.sharded_prefill``) and keeps that slice of the
         KV; the tail rank computes the first token (and, under ``logprobs``, its log-prob rows) and broadcasts it.  The
@@ -871,7 +962,7 @@ class LlamaGlide(LlamaForCausalLM):
                         torch.zeros((bsz, 1, logprobs.top_n), dtype=torch.int64, device=dev))
         if shard.is_tail:
             first, first_lp = self._first_token(self.lm_head(hidden_states[:, hi - lo - 1, :]), sampling, input_len, penalties,
-                                                prompt_state, logprobs)
+                                                prompt_state, logprobs, stop, stop_table)
         shard.broadcast_from_tail(first)
         for t in first_lp or ():
             if t.numel():
@@ -882,7 +973,7 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_tree_decode(self, first_token, cache_lens, prompt_bound: int, tree_shape=None, max_gen_len=64, eos_id=151645,
                           temperature=0.0, sampling=None, penalties=None, prompt_ids=None, prompt_state=None, logprobs=None,
-                          first_logprobs=None):
+                          first_logprobs=None, stop=None, stop_table=None):
         """State of the round loop right after the two prefills (``llama_glide.py:927-991``).
         ``first_token`` [bsz] = the target's first generated token, ``cache_lens`` [bsz] int32 = valid
         rows of every KV cache, ``prompt_bound`` = host-side bound of it.  Also the entry point of
@@ -893,11 +984,17 @@ class LlamaGlide(LlamaForCausalLM):
         the text so far) plus the tokens on node j's path (None at temperature 0: the process-wide default
         LONGSPEC_PENALTIES, else none).  ``logprobs``: the rows on the accepted path fill their columns of ``st.logprobs``
         inside the round and its graph (None at temperature 0: the process-wide default LONGSPEC_LOGPROBS, else none;
-        ``first_logprobs``: the first token's rows, for column 0)."""
+        ``first_logprobs``: the first token's rows, for column 0).  ``stop``: every round tests the columns it wrote against
+        the stops (``stop.py``; None at temperature 0: the process-wide default LONGSPEC_STOP, else none; ``stop_table``: its
+        device table, already built) inside the round and its graph, in front of the one host read; a match ends the loop with
+        that round, the columns of ``output_ids`` / ``spec_mask`` / ``st.logprobs`` behind it go back to their fill and
+        ``st.last_stop`` holds (length, which, match_start).  KV lengths, ``st.token_state`` and the host counters ``count`` /
+        ``num`` / ``emitted`` are not rolled back: a stopped state is final and ``last_stop.length`` is the authority."""
         dev = first_token.device
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         penalties = _resolve_penalties(penalties, temperature, use_env=True)
         logprobs = _resolve_logprobs(logprobs, temperature, use_env=True)
+        stop = _resolve_stop(stop, temperature, use_env=True)
         sh = self.model.layers[-1].self_attn.shard
         if sampling is not None and sh is not None and sh.vocab_parallel:
             raise ValueError("sampling= is not available with a vocabulary-parallel shard")
@@ -929,6 +1026,10 @@ class LlamaGlide(LlamaForCausalLM):
         st.a = 1                              # host mirror of acc_num (G9: the pad id is outside the vocab)
         st.emitted = 1                        # tokens written to output_ids so far (host mirror of emitted_dev)
         st.emitted_dev = torch.ones((bsz,), dtype=torch.int32, device=dev)
+        st.fill = self._tree_output_fill(eos_id)
+        self._begin_stop(st, stop, bsz, dev, stop_table)
+        if st.stop is not None:                              # column 0; a hit ends the loop with its first round
+            self._stop_scan(st, st.emitted_dev, fill=st.fill)
         # HIP graphs of the round, one per `a`: on a GPU; under a KV shard only when its exchange is the peer-store one
         # (kernel launches only: dist.PeerExchange) -- callers that bracket kernels with events switch it off per round
         sh = self.model.layers[-1].self_attn.shard
@@ -968,6 +1069,8 @@ class LlamaGlide(LlamaForCausalLM):
         tokens accepted by the previous round (1..gamma+1).  With ``st.use_graphs`` the round is captured once per
         value of ``a`` into a HIP graph and replayed: the ~370 launches of a round (most of them 4-20 us draft
         kernels the host cannot issue fast enough) become one."""
+        if st.stopped:                                                # a stop= match ended this state: no device work
+            return False
         a = st.a
         state = None
         if st.use_graphs and not st.replayer.disabled and (st.graphs_forced or st.num >= self.GRAPH_AFTER * st.bsz):
@@ -978,6 +1081,7 @@ class LlamaGlide(LlamaForCausalLM):
             state = self._round_device(st, a)
         state = state.tolist()                                        # the round's ONE host read
         a, hit = state[0][0], any(row[1] for row in state)
+        st.stopped = any(row[1] & 2 for row in state)                 # ops.stop_scan raised bit 1
         st.acc_ids = st.acc_pad[:, :a]
         st.a = a
         st.emitted += a
@@ -1025,7 +1129,8 @@ class LlamaGlide(LlamaForCausalLM):
             return
         st.graphs_forced = True
         names = ("cache_lens", "target_cache_lens_for_draft", "draft_cache_lens", "tree_mask", "all_spec", "history_logp_sum",
-                 "acc_pad", "output_ids", "emitted_dev") + (("token_state",) if st.token_state is not None else ())
+                 "acc_pad", "output_ids", "emitted_dev") + (("token_state",) if st.token_state is not None else ()) \
+            + (("stop_state",) if st.stop_state is not None else ())
         lp_bufs = (st.logprobs.token, st.logprobs.top_ids, st.logprobs.top) if st.logprobs is not None else ()
         with rp.guard():
             rp.roll_over(st.emitted)
@@ -1125,6 +1230,9 @@ class LlamaGlide(LlamaForCausalLM):
                 # row j follows the committed text (the root included) and the nodes on its path: mask row j, root column aside
                 llm_logits = ops.penalize_rows(llm_logits, st.token_state, st.penalties, all_spec[:, 1:], tree_mask[:, :, 1:],
                                                bias=st.bias_table)
+            if st.stop is not None and st.stop.min_tokens > 0:
+                # row j predicts column emitted + depth(j): the root the next column, a node its depth further on
+                llm_logits = ops.stop_ban_rows(llm_logits, st.stop.table, base=st.emitted_dev, depth="tree", tree_mask=tree_mask)
             all_llm_pred = self._target_tokens(llm_logits, st.sampling,
                                                position_ids[:, a - 1:a + Fn - 1] if st.sampling is not None else None)
         # ---- A: accept / reject tree collapse + last-layer KV row move (:1104-1116); the accepted rows start at
@@ -1152,6 +1260,8 @@ class LlamaGlide(LlamaForCausalLM):
                                 emitted_dev=st.emitted_dev)
         if st.penalties is not None:                          # the accepted tokens, inside the round (and its graph)
             ops.token_state_add(st.token_state, acc_pad, num=acc_num_t)
+        if st.stop is not None:                               # the stop test on the columns tree_commit wrote; a hit rides in
+            self._stop_scan(st, st.emitted_dev, num=acc_num_t, fill=st.fill, state=state)      # state[:, 1] (bit 1)
         return state
 
     def tree_round_stochastic(self, st) -> bool:

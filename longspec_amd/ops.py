@@ -546,6 +546,97 @@ def logprob_commit(rows, out, base: torch.Tensor, base_add: int = 0, num: Option
                                          _stream()), "ls_logprob_commit")
 
 
+STOP_TABLE_WORDS = 341     # int32 words of a stop table (longspec_amd/stop.py, LS_STOP_TABLE_WORDS)
+
+
+def _stop_table(table, what):
+    if table.dtype != torch.int32 or table.dim() != 1 or table.numel() != STOP_TABLE_WORDS or not table.is_contiguous():
+        raise TypeError(f"{what}: table must be a contiguous int32 [{STOP_TABLE_WORDS}] tensor (Stop.table)")
+    return table.data_ptr()
+
+
+def stop_scan(output_ids: torch.Tensor, table: torch.Tensor, stop_state: torch.Tensor, written: torch.Tensor,
+              written_sub: Optional[torch.Tensor] = None, written_add: int = 0, num: Optional[torch.Tensor] = None,
+              num_const: int = 1, fill: int = 0, state: Optional[torch.Tensor] = None, spec_mask: Optional[torch.Tensor] = None,
+              logprobs=None) -> None:
+    """The stop test of a round or step, behind its commit (``ls_stop_scan``, one launch, one wave per batch row; the definition
+    is ``longspec_amd/stop.py``).  Of ``output_ids`` [b, W] int64, ``written[z] - written_sub[z] + written_add`` columns are
+    written (int32 [b] tensors on the device), the last ``num[z]`` (int64 [b], any stride; None: ``num_const``) by this round.
+    A row of ``stop_state`` [b, 4] int32 that has not stopped and matches a stop of ``table`` (``Stop.table``) among those
+    columns becomes (length, which, match_start, reserved); for such a row and for one that had stopped before, the columns
+    [length, written) of ``output_ids`` go back to ``fill``, of ``spec_mask`` [b, W] int64 to 0 and of ``logprobs`` (the
+    namespace of ``logprobs.py``, W columns) to NaN / -inf / -1, and ``state[z, 1] |= 2`` (``state`` int64 [b, >= 2]: the round's
+    state tensor).  Everything in place."""
+    lp = (logprobs.token, logprobs.top, logprobs.top_ids) if logprobs is not None else ()
+    _dev(output_ids, table, stop_state, written, written_sub, num, state, spec_mask, *lp)
+    if output_ids.dtype != torch.int64 or output_ids.dim() != 2 or output_ids.stride(1) != 1:
+        raise TypeError("stop_scan: output_ids must be int64 [b, W] with contiguous rows")
+    b, W = output_ids.shape
+    tab_p = _stop_table(table, "stop_scan")
+    if stop_state.dtype != torch.int32 or tuple(stop_state.shape) != (b, 4) or not stop_state.is_contiguous():
+        raise TypeError(f"stop_scan: stop_state must be a contiguous int32 [{b}, 4] tensor")
+    num_p, num_s = None, 0
+    if num is not None:
+        if num.dtype != torch.int64 or num.numel() != b or num.dim() != 1:
+            raise TypeError("stop_scan: num must be int64 [b]")
+        num_p, num_s = num.data_ptr(), num.stride(0)
+    elif num_const < 0:
+        raise ValueError(f"stop_scan: num_const={num_const}")
+    state_p, state_s = None, 0
+    if state is not None:
+        if state.dtype != torch.int64 or state.dim() != 2 or state.shape[0] != b or state.shape[1] < 2 or state.stride(1) != 1:
+            raise TypeError("stop_scan: state must be int64 [b, >= 2] with contiguous rows")
+        state_p, state_s = state.data_ptr(), state.stride(0)
+    mask_p, mask_s = None, 0
+    if spec_mask is not None:
+        if spec_mask.dtype != torch.int64 or tuple(spec_mask.shape) != (b, W) or spec_mask.stride(1) != 1:
+            raise TypeError(f"stop_scan: spec_mask must be int64 [{b}, {W}] with contiguous rows")
+        mask_p, mask_s = spec_mask.data_ptr(), spec_mask.stride(0)
+    n, lp_p = 0, (None, None, None)
+    if logprobs is not None:
+        n = logprobs.top.shape[2]
+        for t, shape, dt, name in ((logprobs.token, (b, W), torch.float32, "token"), (logprobs.top, (b, W, n), torch.float32, "top"),
+                                   (logprobs.top_ids, (b, W, n), torch.int64, "top_ids")):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise TypeError(f"stop_scan: logprobs.{name} must be a contiguous {dt} tensor of shape {shape}")
+        lp_p = (logprobs.token.data_ptr(), logprobs.top.data_ptr() if n else None, logprobs.top_ids.data_ptr() if n else None)
+    _C.check(_C.load().ls_stop_scan(output_ids.data_ptr(), b, output_ids.stride(0), W, _len_i32(written, b, "written"),
+                                    _len_i32(written_sub, b, "written_sub"), int(written_add), num_p, num_s, int(num_const),
+                                    tab_p, STOP_TABLE_WORDS, stop_state.data_ptr(), int(fill), state_p, state_s, mask_p, mask_s,
+                                    lp_p[0], lp_p[1], lp_p[2], n, _stream()), "ls_stop_scan")
+
+
+def stop_ban_rows(logits: torch.Tensor, table: torch.Tensor, base: Optional[torch.Tensor] = None,
+                  base_sub: Optional[torch.Tensor] = None, base_add: int = 0, depth: Optional[str] = None,
+                  tree_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The ``min_tokens`` ban on TARGET logits [b, V] or [b, R, V] (16-bit, unit column stride, any row strides), IN PLACE
+    (``ls_stop_ban_rows``, one launch): row r of batch z predicts column ``base[z] - base_sub[z] + base_add + depth(r)`` (int32
+    [b] tensors on the device, None: 0), ``depth`` None: 0, ``"row"``: r, ``"tree"``: the row sum of ``tree_mask[z, r, 1:]``
+    (int64 [b, R, C]).  Where that column is below the table's ``min_tokens``, the entries of its token ids become -inf; every
+    other element keeps its bits.  Returns ``logits``."""
+    _dev(logits, table, base, base_sub, tree_mask)
+    if logits.dim() not in (2, 3) or logits.dtype not in (torch.float16, torch.bfloat16) or logits.stride(-1) != 1:
+        raise TypeError("stop_ban_rows: logits must be fp16 / bf16 [b, V] or [b, R, V] with unit column stride")
+    x = logits if logits.dim() == 3 else logits.unsqueeze(1)
+    b, R, V = x.shape
+    if (R > 1 and x.stride(1) < V) or (b > 1 and x.stride(0) < V):
+        raise ValueError("stop_ban_rows: overlapping rows")
+    tab_p = _stop_table(table, "stop_ban_rows")
+    if depth not in (None, "row", "tree"):
+        raise ValueError(f"stop_ban_rows: depth={depth!r} (None, 'row' or 'tree')")
+    mode = {None: 0, "row": 1, "tree": 2}[depth]
+    mask_p = mask_sb = mask_sr = mask_c = 0
+    if mode == 2:
+        if tree_mask is None or tree_mask.dtype != torch.int64 or tree_mask.dim() != 3 or tuple(tree_mask.shape[:2]) != (b, R) \
+                or tree_mask.stride(2) != 1:
+            raise TypeError(f"stop_ban_rows: tree_mask must be int64 [{b}, {R}, C] with unit column stride")
+        mask_p, mask_sb, mask_sr, mask_c = tree_mask.data_ptr(), tree_mask.stride(0), tree_mask.stride(1), tree_mask.shape[2]
+    _C.check(_C.load().ls_stop_ban_rows(x.data_ptr(), b, R, V, _dtype(x), x.stride(0), max(x.stride(1), V), tab_p, STOP_TABLE_WORDS,
+                                        _len_i32(base, b, "base"), _len_i32(base_sub, b, "base_sub"), int(base_add), mode,
+                                        mask_p or None, mask_sb, mask_sr, mask_c, _stream()), "ls_stop_ban_rows")
+    return logits
+
+
 TOPK_CHUNK = 8192          # logits per stage-1 record (ls_topk_chunk(); checked at first use)
 
 
