@@ -447,6 +447,30 @@ int ls_stop_ban_rows(void* logits, int b, int rows, int vocab, int dtype, int64_
                      int table_words, const int32_t* base, const int32_t* base_sub, int base_add, int depth_mode,
                      const int64_t* mask, int64_t mask_stride_b, int64_t mask_stride_r, int mask_cols, void* stream);
 
+/* The drafter of prompt-lookup (n-gram) speculation (lookup_generate; csrc/lookup.hip; no counterpart in the reference, whose
+ * every loop needs a trained draft layer).  The text of batch row z is T = prompt_ids[z, :il] ++ output_ids[z, :w], il =
+ * input_len[z] clamped to 0..prompt_cols, w = cache_lens[z] - input_len[z] + 1 clamped to 0..out_cap (the columns written so far,
+ * the last round's bonus token included), L = il + w; prompt padding and output columns at or behind w are never read.  For an
+ * end e in 1 .. L-1, m(e) is the largest k <= min(max_ngram, e) with T[e-k:e] == T[L-k:L] (ids compared as 64-bit integers,
+ * occurrences may overlap the suffix); among the ends with m(e) >= min_ngram the largest m wins, then the largest e.
+ *   spec_buffer [b, gamma+1] int64 dense   [z, 1+i] = T[e + i mod (L - e)], i < gamma: the continuation, read on into the draft
+ *                                          itself where it reaches the end of the text; no candidate: T[L-1].  Column 0 is kept.
+ *   info        [b, 2] int32               (n, e) = (m of the winner, its end), or (0, -1)
+ *   hist        [b, max_ngram+1] int64     hist[z, n] += 1 (one writer per row, no atomics); may be NULL
+ * len_bound is a HOST-side upper bound of L (the bound the round's attention launches are sized from): it sizes the grid and the
+ * workspace, nothing on the device is read for it; a longer text is searched over its first ends only and never read out of range.
+ * Two launches: (chunks of LS_NGRAM_CHUNK ends, b) workgroups write one 64-bit record (m << 32 | e) each into the workspace -- one
+ * pass over the text, 8-byte loads --, one wave per row takes their maximum and writes the results.  Every record is rewritten by
+ * every call: nothing to zero between calls, safe inside a replayed graph.  Exact; no floating point.  LS_ERR_INVALID_ARG, before
+ * any launch: gamma outside 1..15, max_ngram outside 1..8, min_ngram outside 1..max_ngram, b outside 1..65535, a column count
+ * outside 1..2^30-1 or above its row stride, misaligned pointers. */
+#define LS_NGRAM_CHUNK 1024
+size_t ls_ngram_workspace_bytes(int b, int64_t len_bound);
+int ls_ngram_draft(const int64_t* prompt_ids, int64_t prompt_stride_b, int prompt_cols, const int32_t* input_len,
+                   const int64_t* output_ids, int64_t out_stride_b, int out_cap, const int32_t* cache_lens, int b, int64_t len_bound,
+                   int gamma, int max_ngram, int min_ngram, int64_t* spec_buffer, int32_t* info, int64_t* hist, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* ls_logprob_topk and ls_argmax_rows with the lm_head SHARDED BY VOCABULARY over the ranks of a node (no counterpart in the reference, which
  * replicates: llama_glide.py:474).  A "record" is what stage 1 produces per (8192-logit chunk, row): the chunk's max, its sum of
  * exp(x - max) and its k largest logits with their GLOBAL columns -- rows * (2 + 2k) floats per chunk slot, chunk-major.

@@ -26,6 +26,7 @@ from .sampling import resolve as _resolve_sampling
 from .penalties import resolve as _resolve_penalties
 from .logprobs import new_buffers as _logprob_buffers, resolve as _resolve_logprobs
 from .stop import new_state as _stop_state, resolve as _resolve_stop, result_of as _stop_result
+from .lookup import check as _lookup_check
 from .llama import (DecodeLinear, LlamaForCausalLM, LlamaMLP, LlamaRMSNorm, chunked_causal_prefill,
                     project_qkv, _default_ops)
 
@@ -845,6 +846,180 @@ class LlamaGlide(LlamaForCausalLM):
         st.num += bsz
         st.emitted += n_ok
         if st.emitted - 1 + gamma + 2 > output_ids.size(1):
+            return False
+        return not hit
+
+    # ------------------------------------------------------------------------------------------
+    @torch.inference_mode()
+    def lookup_generate(self, input_ids, prompt_length, gamma=7, max_ngram=3, min_ngram=1, max_gen_len=64, eos_id=151645,
+                        sampling=None, penalties=None, logprobs=None, stop=None):
+        """Prompt-lookup (n-gram) speculation (no counterpart in the reference): chain speculation whose drafter is the text
+        itself -- the ``gamma`` tokens that followed the most recent earlier occurrence of the last ``min_ngram .. max_ngram``
+        tokens of prompt + output (``lookup.py``) -- verified exactly like ``spec_generate``.  No draft weights, no draft KV,
+        no draft prefill and no draft pass: the glide layer is never called, so a model without a draft checkpoint can use
+        it.  A round is one ``ops.ngram_draft`` and one (gamma + 1)-row target pass.  Same return tuple as ``spec_generate``;
+        ``sampling`` / ``penalties`` / ``logprobs`` / ``stop`` act on the verification rows as they do there
+        (``self.last_logprobs``, ``self.last_stop``); ``self.last_lookup`` holds ``hist`` [bsz, max_ngram + 1] int64 -- how many
+        rounds matched at which length, [:, 0] = none -- and ``info`` [bsz, 2] int32 = (n, e) of the last round, both on the
+        device.  There is no ``temperature=``: the reference's T > 0 rejection needs the draft logits a lookup does not have."""
+        assert input_ids is not None, "please give the input"
+        gamma, max_ngram, min_ngram = _lookup_check(gamma, max_ngram, min_ngram)
+        sampling = _resolve_sampling(sampling, None, use_env=True)
+        pen = _resolve_penalties(penalties, None, use_env=True)
+        lpc = _resolve_logprobs(logprobs, None, use_env=True)
+        stp = _resolve_stop(stop, None, use_env=True)
+        stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
+        self._clear_shard()
+        bsz = input_ids.size(0)
+        assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
+        dev = input_ids.device
+        self.set_max_gen_len(max_gen_len + 128)
+        P = int(input_ids.size(1))
+        self._set_hints(P, P)
+        hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
+        input_len = prompt_length
+        rows = torch.arange(bsz, device=dev)
+        logits = self.lm_head(hidden_states[rows, input_len - 1, :])
+        cache_lens = input_ids.new_zeros((bsz)).int() + input_len.int()
+        pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
+        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab)
+        st = self.begin_lookup_decode(first, cache_lens, input_len, P, input_ids, gamma, max_ngram, min_ngram, max_gen_len, eos_id,
+                                      sampling=sampling, penalties=penalties, prompt_state=pstate, logprobs=logprobs,
+                                      first_logprobs=first_lp, stop=stop, stop_table=stab)
+        self.last_logprobs = st.logprobs
+        self.last_stop = st.last_stop
+        self.last_lookup = st.last_lookup
+        _sync(input_ids)
+        start_time = time.time()
+        for out_index in range(1, max_gen_len):
+            if not self.lookup_round(st):
+                break
+        _sync(input_ids)
+        elapsed_time = time.time() - start_time
+        return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
+
+    def begin_lookup_decode(self, first_token, cache_lens, input_len, prompt_bound: int, prompt_ids, gamma=7, max_ngram=3,
+                            min_ngram=1, max_gen_len=64, eos_id=151645, sampling=None, penalties=None, prompt_state=None,
+                            logprobs=None, first_logprobs=None, stop=None, stop_table=None):
+        """State of the prompt-lookup loop right after the target's prefill: the arguments of ``begin_chain_decode`` that have
+        a meaning without a drafter, plus ``prompt_ids`` [bsz, P] -- here not optional: ``prompt_ids[z, :input_len[z]]`` is the
+        front of the text the drafter searches (and, under ``penalties``, the source of the prompt flags).  Also the entry point
+        of benchmarks that time ``lookup_round`` on synthetic KV.  ``st.hist`` / ``st.info`` (``st.last_lookup``) are what
+        ``ops.ngram_draft`` keeps; ``st.replayer`` replays the round from one HIP graph per tier (``lookup_round``)."""
+        gamma, max_ngram, min_ngram = _lookup_check(gamma, max_ngram, min_ngram)
+        bsz = first_token.size(0)
+        dev = first_token.device
+        sampling = _resolve_sampling(sampling, None, use_env=True)
+        penalties = _resolve_penalties(penalties, None, use_env=True)
+        logprobs = _resolve_logprobs(logprobs, None, use_env=True)
+        stop = _resolve_stop(stop, None, use_env=True)
+        st = _DecodeState(gamma=gamma, max_ngram=max_ngram, min_ngram=min_ngram, bsz=bsz, P=int(prompt_bound),
+                          max_gen_len=max_gen_len, count=0, num=0, emitted=1, rounds=0, sampling=sampling)
+        st.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if sampling is not None else None
+        st.prompt_ids = prompt_ids.to(device=dev, dtype=torch.int64)
+        if st.prompt_ids.stride(-1) != 1:
+            st.prompt_ids = st.prompt_ids.contiguous()
+        self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
+        st.chain_mask = None
+        if penalties is not None:
+            # verification row i follows the draft tokens spec_buffer[:, 1 : i + 1]
+            st.chain_mask = torch.ones((gamma + 1, gamma), dtype=torch.int64, device=dev).tril(-1)
+        self._begin_logprobs(st, logprobs, bsz, max_gen_len + gamma, dev, first_logprobs)
+        st.output_ids = first_token.new_zeros((bsz, max_gen_len + gamma))
+        st.spec_mask = first_token.new_zeros((bsz, max_gen_len + gamma))
+        st.output_ids[:, 0] = first_token
+        st.cache_lens = cache_lens
+        st.input_len = input_len
+        st.input_len_i32 = input_len.to(device=dev, dtype=torch.int32).view(bsz).contiguous()
+        st.spec_buffer = st.output_ids.new_zeros((bsz, gamma + 1))
+        st.spec_buffer[:, 0] = st.output_ids[:, 0]
+        # what chain_commit keeps for a drafter with a cache of its own: scratch here
+        st.draft_cache_lens = cache_lens.clone()
+        st.next_spec_start_token = st.output_ids.new_zeros((bsz, 2))
+        st.info = torch.zeros((bsz, 2), dtype=torch.int32, device=dev)
+        st.hist = torch.zeros((bsz, max_ngram + 1), dtype=torch.int64, device=dev)
+        st.last_lookup = SimpleNamespace(hist=st.hist, info=st.info)
+        st.eos = self._stop_id(eos_id, "spec")
+        self._begin_stop(st, stop, bsz, dev, stop_table)
+        if st.stop is not None:                              # column 0; a hit ends the loop with its first round
+            self._stop_scan(st, st.cache_lens, st.input_len_i32, 1)
+        st.use_graphs = bool(dev.type == "cuda" and bsz == 1 and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
+        P, rows = st.P, gamma + 2                          # (the replayer holds no reference to the state that holds it)
+        st.replayer = GraphReplayer(self, lambda bound: (P + bound + rows, P + bound + rows), st.output_ids.size(1), "lookup round")
+        return st
+
+    def _lookup_device(self, st):
+        """The device work of one lookup round (no host read inside, no host-side parameter): the draft from the text, then
+        the verification half of ``chain_round``, operator for operator.  The drafter's grid is sized from the bound the
+        round's attention launches are sized from (``_set_hints``: the eager round's, or the graph tier's).  Returns state
+        [bsz, 2] = (correct_len, EOS hit | 2 * stop hit)."""
+        gamma = st.gamma
+        output_ids, cache_lens, spec_buffer = st.output_ids, st.cache_lens, st.spec_buffer
+        bound = self.model.layers[-1].self_attn.kv_len_hint or st.P + output_ids.size(1)
+        self.ops.ngram_draft(st.prompt_ids, st.input_len_i32, output_ids, cache_lens, bound, gamma, st.max_ngram, st.min_ngram,
+                             spec_buffer, info=st.info, hist=st.hist)
+        hidden_states = self.model.forward(spec_buffer, cache_lens=cache_lens, exec_type="decoding").last_hidden_state
+        llm_verify_logits = self.lm_head(hidden_states[:, -gamma - 1:, :])
+        if st.penalties is not None:
+            llm_verify_logits = self.ops.penalize_rows(llm_verify_logits, st.token_state, st.penalties, spec_buffer[:, 1:],
+                                                       st.chain_mask, bias=st.bias_table)
+        if st.stop is not None and st.stop.min_tokens > 0:   # row i predicts column cache_lens - input_len + 1 + i
+            llm_verify_logits = self.ops.stop_ban_rows(llm_verify_logits, st.stop.table, base=cache_lens, base_sub=st.input_len_i32,
+                                                       base_add=1, depth="row")
+        # (sampling: verification row i was rotated to position cache_lens + i)
+        llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
+                                                cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
+        lp_rows = lp_base = None
+        if st.logprobs is not None:
+            lp_rows = self.ops.token_logprobs(llm_verify_logits, llm_verify_output, st.logprobs.temperature, st.logprobs.top_n)
+            lp_base = (cache_lens - st.input_len_i32).to(torch.int32)
+        # acceptance by cumulative match, verified ids + bonus token -> output_ids, cache_lens += correct_len, and the bonus
+        # token -> spec_buffer[:, 0], the next round's start token
+        state = self.ops.chain_commit(llm_verify_output, spec_buffer, output_ids, cache_lens, st.draft_cache_lens, st.input_len_i32,
+                                      st.next_spec_start_token, st.eos)
+        if st.penalties is not None:                         # the correct_len tokens this round wrote, before the host read
+            self.ops.token_state_add(st.token_state, llm_verify_output, num=state[:, 0])
+        if lp_rows is not None:                              # ... and their log-probs, to the columns chain_commit wrote
+            self.ops.logprob_commit(lp_rows, st.logprobs, lp_base, base_add=1, num=state[:, 0])
+        if st.stop is not None:                              # the stop test on those columns; a hit rides in state[:, 1] (bit 1)
+            self._stop_scan(st, cache_lens, st.input_len_i32, 1, num=state[:, 0], state=state)
+        return state
+
+    def lookup_round(self, st) -> bool:
+        """One round of ``lookup_generate``: the draft from the text, one (gamma + 1)-row target pass, acceptance by cumulative
+        match.  False = stop (EOS, a ``stop=`` match or the buffer is full); on a state a ``stop=`` match has ended, False at
+        once.  Unlike the glide chain round this one has a static shape -- no ``double_flag``, no draft cache --, so on a GPU
+        it is captured into ONE HIP graph per tier after GRAPH_AFTER eager rounds and replayed, as ``vanilla_step`` is."""
+        if st.stopped:
+            return False
+        gamma, bsz = st.gamma, st.bsz
+        state = None
+        if st.use_graphs and st.rounds >= self.GRAPH_AFTER:
+            rp, device_round = st.replayer, partial(self._lookup_device, st)
+            done = False
+            with rp.guard():
+                rp.roll_over(st.emitted)
+                if rp.captured(None):
+                    state = rp.replay(None)
+                else:
+                    state = rp.warm(None, device_round)               # the warm-up round is this call's round
+                    rp.capture(None, device_round)
+                done = True
+            if not done:
+                st.use_graphs = False
+                state = rp.result if rp.issued else None              # a warm-up round that was issued IS the round
+        if state is None:
+            bound = st.P + st.emitted + gamma + 2
+            self._set_hints(bound, bound)
+            state = self._lookup_device(st)
+        st.rounds += 1
+        state = state.tolist()                                        # the round's ONE host read
+        n_ok, hit = state[0][0], any(row[1] for row in state)
+        st.stopped = any(row[1] & 2 for row in state)
+        st.count += n_ok - 1
+        st.num += bsz
+        st.emitted += n_ok
+        if st.emitted - 1 + gamma + 2 > st.output_ids.size(1):
             return False
         return not hit
 

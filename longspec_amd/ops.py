@@ -15,6 +15,8 @@ One function per reference seam of the draft-then-verify round:
                          no counterpart in the reference)
   penalize_rows / token_state_add   repetition / presence / frequency penalties and a logit bias on the target's logits, per
                          row from that row's own history, and the [batch, vocab] state they read (penalties=; no counterpart)
+  ngram_draft            the drafter of prompt-lookup speculation: the continuation of the most recent earlier occurrence of
+                         the text's last tokens (lookup_generate; no counterpart)
   token_logprobs / logprob_commit   log-prob of every emitted token under the distribution it was taken from and the row's
                          top-n alternatives; the accepted rows' results -> the tokens' output columns (logprobs=; no counterpart)
   tree_commit / tree_commit_stochastic   end of a round at temperature 0 / > 0  llama_glide.py:1093-1121
@@ -107,7 +109,7 @@ _gemm_ws = _ZeroedWorkspace()
 def workspace_tensors():
     """The scratch buffers currently handed out (a captured HIP graph keeps them alive: it holds their addresses)."""
     return (list(_ws._buf.values()) + list(_gemm_ws._buf.values()) + list(_sample_ws._buf.values())
-            + list(_logprob_ws._buf.values()))
+            + list(_logprob_ws._buf.values()) + list(_ngram_ws._buf.values()))
 
 
 _linear_need = {}            # (shape key) -> workspace bytes of the launch plan
@@ -635,6 +637,55 @@ def stop_ban_rows(logits: torch.Tensor, table: torch.Tensor, base: Optional[torc
                                         _len_i32(base, b, "base"), _len_i32(base_sub, b, "base_sub"), int(base_add), mode,
                                         mask_p or None, mask_sb, mask_sr, mask_c, _stream()), "ls_stop_ban_rows")
     return logits
+
+
+_ngram_ws = _Workspace()     # its own buffer, as _sample_ws: a captured round holds its address
+NGRAM_CHUNK = 1024         # candidate ends per stage-1 workgroup of ngram_draft (LS_NGRAM_CHUNK)
+NGRAM_MAX_GAMMA, NGRAM_MAX_N = 15, 8
+
+
+def ngram_draft(prompt_ids: torch.Tensor, input_len: torch.Tensor, output_ids: torch.Tensor, cache_lens: torch.Tensor,
+                len_bound: int, gamma: int, max_ngram: int, min_ngram: int, spec_buffer: torch.Tensor,
+                info: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The drafter of prompt-lookup speculation (``ls_ngram_draft``, two launches; the definition is
+    ``longspec_amd/lookup.py``).  The text of row z is ``prompt_ids[z, :input_len[z]] ++ output_ids[z, :cache_lens[z] -
+    input_len[z] + 1]`` (int64 [b, P] / [b, W] with contiguous rows, any row stride; int32 [b] lengths on the device); the
+    continuation of the most recent earlier occurrence of its longest suffix of ``min_ngram .. max_ngram`` tokens goes to
+    ``spec_buffer[:, 1:]`` (contiguous int64 [b, gamma + 1]; column 0 is kept), ``hist[z, n] += 1`` (contiguous int64
+    [b, max_ngram + 1], optional).  ``len_bound``: a HOST-side upper bound of the text lengths, which sizes the grid -- nothing
+    is read from the device.  Returns ``info`` int32 [b, 2] = (n, e): the matched length and the end of the occurrence, or
+    (0, -1)."""
+    _dev(prompt_ids, input_len, output_ids, cache_lens, spec_buffer, info, hist)
+    for t, name in ((prompt_ids, "prompt_ids"), (output_ids, "output_ids")):
+        if t.dtype != torch.int64 or t.dim() != 2 or t.stride(1) != 1:
+            raise TypeError(f"ngram_draft: {name} must be int64 [b, columns] with contiguous rows")
+    b = output_ids.shape[0]
+    if prompt_ids.shape[0] != b or (b > 1 and (prompt_ids.stride(0) < prompt_ids.shape[1] or output_ids.stride(0) < output_ids.shape[1])):
+        raise ValueError("ngram_draft: prompt_ids and output_ids must have one row per batch row, rows apart")
+    if not (1 <= gamma <= NGRAM_MAX_GAMMA and 1 <= max_ngram <= NGRAM_MAX_N and 1 <= min_ngram <= max_ngram):
+        raise ValueError(f"ngram_draft: gamma={gamma} (1..{NGRAM_MAX_GAMMA}), max_ngram={max_ngram} (1..{NGRAM_MAX_N}), "
+                         f"min_ngram={min_ngram} (1..max_ngram)")
+    if spec_buffer.dtype != torch.int64 or tuple(spec_buffer.shape) != (b, gamma + 1) or not spec_buffer.is_contiguous():
+        raise TypeError(f"ngram_draft: spec_buffer must be a contiguous int64 [{b}, {gamma + 1}] tensor")
+    if int(len_bound) < 1:
+        raise ValueError(f"ngram_draft: len_bound={len_bound}")
+    dev = output_ids.device
+    if info is None:
+        info = torch.empty((b, 2), dtype=torch.int32, device=dev)
+    elif info.dtype != torch.int32 or tuple(info.shape) != (b, 2) or not info.is_contiguous():
+        raise TypeError(f"ngram_draft: info must be a contiguous int32 [{b}, 2] tensor")
+    if hist is not None and (hist.dtype != torch.int64 or tuple(hist.shape) != (b, max_ngram + 1) or not hist.is_contiguous()):
+        raise TypeError(f"ngram_draft: hist must be a contiguous int64 [{b}, {max_ngram + 1}] tensor")
+    lib = _C.load()
+    need = lib.ls_ngram_workspace_bytes(b, int(len_bound))
+    ws = _ngram_ws.get(dev, max(need, 1))
+    _C.check(lib.ls_ngram_draft(prompt_ids.data_ptr(), max(prompt_ids.stride(0), prompt_ids.shape[1]), prompt_ids.shape[1],
+                                _len_i32(input_len, b, "input_len"), output_ids.data_ptr(),
+                                max(output_ids.stride(0), output_ids.shape[1]), output_ids.shape[1],
+                                _len_i32(cache_lens, b, "cache_lens"), b, int(len_bound), gamma, max_ngram, min_ngram,
+                                spec_buffer.data_ptr(), info.data_ptr(), hist.data_ptr() if hist is not None else None,
+                                ws.data_ptr(), ws.numel(), _stream()), "ls_ngram_draft")
+    return info
 
 
 TOPK_CHUNK = 8192          # logits per stage-1 record (ls_topk_chunk(); checked at first use)
