@@ -471,6 +471,33 @@ int ls_ngram_draft(const int64_t* prompt_ids, int64_t prompt_stride_b, int promp
                    int gamma, int max_ngram, int min_ngram, int64_t* spec_buffer, int32_t* info, int64_t* hist, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* The TREE drafter of prompt-lookup speculation (lookup_generate(branches=B); csrc/lookup_tree.hip): up to B distinct continuations
+ * per round, laid out as a level-major tree that ls_verify_attention's packed tree mask, ls_tree_verify_inputs, ls_tree_collapse and
+ * ls_tree_commit take as it is.  The text, m(e), the candidates and their key (m, e) are ls_ngram_draft's, but for the output
+ * columns that count as text: w = written[z] clamped to 0..out_cap (the tree round's emitted_dev; its cache_lens lags the text by
+ * the tokens the next pass feeds again).  The LS_NGRAM_TOP candidates with the largest keys are walked in descending order; one is
+ * kept when its gamma-token continuation c_e[i] = T[e + i mod (L - e)] differs from every kept one, until `branches` are kept (nb
+ * of them).  Slot j < nb holds kept candidate j, a slot >= nb a copy of slot 0; with nb = 0 every slot is T[L-1] repeated.  Slot 0
+ * is what ls_ngram_draft drafts from the same text.  F = 1 + branches * gamma nodes, the root first; node 1 + (d-1)*branches + j
+ * is depth d = 1..gamma of branch j.
+ *   all_spec  [b, F] int64 dense        [z, 1 + (d-1)*branches + j] = slot_j[d-1]; column 0 (the root) is kept
+ *   tree_mask [b, F, F] int64 dense     rows 1.. in full: 1 at column 0 and at the nodes of the row's branch at depths <= its own,
+ *                                       else 0; row 0 is kept
+ *   info      [b, branches, 2] int32    (n, e) of the slot's candidate; (0, -1) for slots >= nb
+ *   hist      [b, max_ngram+1] int64    hist[z, n of slot 0] += 1: comparable with ls_ngram_draft's; may be NULL
+ *   hist_nb   [b, branches+1] int64     hist_nb[z, nb] += 1; may be NULL
+ * Two launches, shaped like ls_ngram_draft's: (chunks of LS_NGRAM_CHUNK ends, b) workgroups leave their LS_NGRAM_TOP largest keys in
+ * descending order, zero padded, as records of 8 bytes in the workspace (one pass over the text); one wave per row takes the row's
+ * LS_NGRAM_TOP largest, loads the continuations, does the distinctness walk and writes everything above.  No atomics; every record
+ * and every output is rewritten by every call: safe inside a replayed graph.  Exact.  LS_ERR_INVALID_ARG, before any launch: as
+ * ls_ngram_draft, and branches outside 1..LS_NGRAM_TOP. */
+#define LS_NGRAM_TOP 8
+size_t ls_ngram_tree_workspace_bytes(int b, int64_t len_bound);      /* b * chunks * LS_NGRAM_TOP records of 8 bytes */
+int ls_ngram_tree_draft(const int64_t* prompt_ids, int64_t prompt_stride_b, int prompt_cols, const int32_t* input_len,
+                        const int64_t* output_ids, int64_t out_stride_b, int out_cap, const int32_t* written, int b, int64_t len_bound,
+                        int gamma, int branches, int max_ngram, int min_ngram, int64_t* all_spec, int64_t* tree_mask, int32_t* info,
+                        int64_t* hist, int64_t* hist_nb, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ls_logprob_topk and ls_argmax_rows with the lm_head SHARDED BY VOCABULARY over the ranks of a node (no counterpart in the reference, which
  * replicates: llama_glide.py:474).  A "record" is what stage 1 produces per (8192-logit chunk, row): the chunk's max, its sum of
  * exp(x - max) and its k largest logits with their GLOBAL columns -- rows * (2 + 2k) floats per chunk slot, chunk-major.

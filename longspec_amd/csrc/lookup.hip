@@ -16,11 +16,10 @@
 // Every record is rewritten by every call and nothing is counted with atomics, so the pair replays from a captured graph.  Every
 // index is clamped before use: a prompt read is below min(il, prompt columns), an output read below min(w, output columns), and a
 // text longer than the host's bound only loses its most recent ends.
-#include "ls_common.h"
+#include "lookup_text.h"
 
 namespace {
 
-constexpr int NG_WAVE = 64;
 constexpr int NG_THREADS = 256;
 constexpr int NG_PER = 4;
 constexpr int NG_CHUNK = NG_THREADS * NG_PER;
@@ -44,34 +43,10 @@ struct NgramArgs {
     unsigned long long* rec; // [b, nchunks]
 };
 
-// the row's text: il prompt tokens, w output tokens (both inside their buffers)
-struct Text {
-    const int64_t* p;
-    const int64_t* o;
-    int il, L;
-    __device__ __forceinline__ int64_t at(int i) const { return i < il ? p[i] : o[i - il]; }   // 0 <= i < L
-};
-
 __device__ __forceinline__ Text text_of(const NgramArgs& a, int z) {
-    Text t;
-    t.p = a.prompt + (long)z * a.prompt_sb;
-    t.o = a.out + (long)z * a.out_sb;
     const long il_raw = a.input_len[z];
-    const long w_raw = (long)a.cache_lens[z] - il_raw + 1;
-    t.il = il_raw < 0 ? 0 : il_raw > a.prompt_cols ? a.prompt_cols : (int)il_raw;
-    const int w = w_raw < 0 ? 0 : w_raw > a.out_cap ? a.out_cap : (int)w_raw;
-    t.L = t.il + w;                                                // <= 2^31 - 2: the host bounds both column counts by 2^30 - 1
-    return t;
-}
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, off, NG_WAVE), hi = __shfl_xor((unsigned)(v >> 32), off, NG_WAVE);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o > v ? o : v;
-    }
-    return v;
+    return text_from(a.prompt + (long)z * a.prompt_sb, a.prompt_cols, a.out + (long)z * a.out_sb, a.out_cap, il_raw,
+                     (long)a.cache_lens[z] - il_raw + 1);
 }
 
 __global__ __launch_bounds__(NG_THREADS) void ngram_match_kernel(NgramArgs a) {

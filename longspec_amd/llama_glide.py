@@ -852,7 +852,7 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def lookup_generate(self, input_ids, prompt_length, gamma=7, max_ngram=3, min_ngram=1, max_gen_len=64, eos_id=151645,
-                        sampling=None, penalties=None, logprobs=None, stop=None):
+                        sampling=None, penalties=None, logprobs=None, stop=None, branches=1):
         """Prompt-lookup (n-gram) speculation (no counterpart in the reference): chain speculation whose drafter is the text
         itself -- the ``gamma`` tokens that followed the most recent earlier occurrence of the last ``min_ngram .. max_ngram``
         tokens of prompt + output (``lookup.py``) -- verified exactly like ``spec_generate``.  No draft weights, no draft KV,
@@ -861,9 +861,17 @@ class LlamaGlide(LlamaForCausalLM):
         ``sampling`` / ``penalties`` / ``logprobs`` / ``stop`` act on the verification rows as they do there
         (``self.last_logprobs``, ``self.last_stop``); ``self.last_lookup`` holds ``hist`` [bsz, max_ngram + 1] int64 -- how many
         rounds matched at which length, [:, 0] = none -- and ``info`` [bsz, 2] int32 = (n, e) of the last round, both on the
-        device.  There is no ``temperature=``: the reference's T > 0 rejection needs the draft logits a lookup does not have."""
+        device.  There is no ``temperature=``: the reference's T > 0 rejection needs the draft logits a lookup does not have.
+
+        ``branches=B`` (2..8; ``B * gamma + gamma + 1 <= 80`` rows): a round drafts up to B distinct continuations
+        (``ops.ngram_tree_draft``, ``lookup.py``) as a level-major tree and verifies them in ONE pass with the verification and
+        accept halves of ``tree_round``.  ``output_ids`` / ``spec_mask`` are then [bsz, max_gen_len + gamma + 1], filled like
+        ``tree_spec_generate``'s, and the loop ends by its rules; ``last_lookup`` also holds ``branches``, ``hist_nb``
+        [bsz, B + 1] (rounds by the number of distinct continuations found) and ``won`` [bsz, B] (rounds by the branch of the
+        deepest accepted node, counted when a draft token was accepted), and its ``info`` is [bsz, B, 2].  ``branches=1`` is
+        the chain loop above, unchanged."""
         assert input_ids is not None, "please give the input"
-        gamma, max_ngram, min_ngram = _lookup_check(gamma, max_ngram, min_ngram)
+        gamma, max_ngram, min_ngram = _lookup_check(gamma, max_ngram, min_ngram, branches)
         sampling = _resolve_sampling(sampling, None, use_env=True)
         pen = _resolve_penalties(penalties, None, use_env=True)
         lpc = _resolve_logprobs(logprobs, None, use_env=True)
@@ -873,7 +881,7 @@ class LlamaGlide(LlamaForCausalLM):
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
         dev = input_ids.device
-        self.set_max_gen_len(max_gen_len + 128)
+        self.set_max_gen_len(max_gen_len + (128 if branches == 1 else 256))      # (a tree pass appends up to 80 rows)
         P = int(input_ids.size(1))
         self._set_hints(P, P)
         hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
@@ -885,7 +893,7 @@ class LlamaGlide(LlamaForCausalLM):
         first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab)
         st = self.begin_lookup_decode(first, cache_lens, input_len, P, input_ids, gamma, max_ngram, min_ngram, max_gen_len, eos_id,
                                       sampling=sampling, penalties=penalties, prompt_state=pstate, logprobs=logprobs,
-                                      first_logprobs=first_lp, stop=stop, stop_table=stab)
+                                      first_logprobs=first_lp, stop=stop, stop_table=stab, branches=branches)
         self.last_logprobs = st.logprobs
         self.last_stop = st.last_stop
         self.last_lookup = st.last_lookup
@@ -900,19 +908,24 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_lookup_decode(self, first_token, cache_lens, input_len, prompt_bound: int, prompt_ids, gamma=7, max_ngram=3,
                             min_ngram=1, max_gen_len=64, eos_id=151645, sampling=None, penalties=None, prompt_state=None,
-                            logprobs=None, first_logprobs=None, stop=None, stop_table=None):
+                            logprobs=None, first_logprobs=None, stop=None, stop_table=None, branches=1):
         """State of the prompt-lookup loop right after the target's prefill: the arguments of ``begin_chain_decode`` that have
         a meaning without a drafter, plus ``prompt_ids`` [bsz, P] -- here not optional: ``prompt_ids[z, :input_len[z]]`` is the
         front of the text the drafter searches (and, under ``penalties``, the source of the prompt flags).  Also the entry point
         of benchmarks that time ``lookup_round`` on synthetic KV.  ``st.hist`` / ``st.info`` (``st.last_lookup``) are what
-        ``ops.ngram_draft`` keeps; ``st.replayer`` replays the round from one HIP graph per tier (``lookup_round``)."""
-        gamma, max_ngram, min_ngram = _lookup_check(gamma, max_ngram, min_ngram)
+        ``ops.ngram_draft`` keeps; ``st.replayer`` replays the round from one HIP graph per tier (``lookup_round``).
+        ``branches >= 2``: the state of the tree round instead (``_begin_lookup_tree``)."""
+        gamma, max_ngram, min_ngram = _lookup_check(gamma, max_ngram, min_ngram, branches)
         bsz = first_token.size(0)
         dev = first_token.device
         sampling = _resolve_sampling(sampling, None, use_env=True)
         penalties = _resolve_penalties(penalties, None, use_env=True)
         logprobs = _resolve_logprobs(logprobs, None, use_env=True)
         stop = _resolve_stop(stop, None, use_env=True)
+        if branches > 1:
+            return self._begin_lookup_tree(first_token, cache_lens, input_len, int(prompt_bound), prompt_ids, gamma, branches,
+                                           max_ngram, min_ngram, max_gen_len, eos_id, sampling, penalties, prompt_state, logprobs,
+                                           first_logprobs, stop, stop_table)
         st = _DecodeState(gamma=gamma, max_ngram=max_ngram, min_ngram=min_ngram, bsz=bsz, P=int(prompt_bound),
                           max_gen_len=max_gen_len, count=0, num=0, emitted=1, rounds=0, sampling=sampling)
         st.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if sampling is not None else None
@@ -992,6 +1005,8 @@ class LlamaGlide(LlamaForCausalLM):
         it is captured into ONE HIP graph per tier after GRAPH_AFTER eager rounds and replayed, as ``vanilla_step`` is."""
         if st.stopped:
             return False
+        if getattr(st, "branches", 1) > 1:
+            return self._lookup_tree_round(st)
         gamma, bsz = st.gamma, st.bsz
         state = None
         if st.use_graphs and st.rounds >= self.GRAPH_AFTER:
@@ -1020,6 +1035,124 @@ class LlamaGlide(LlamaForCausalLM):
         st.num += bsz
         st.emitted += n_ok
         if st.emitted - 1 + gamma + 2 > st.output_ids.size(1):
+            return False
+        return not hit
+
+    def _begin_lookup_tree(self, first_token, cache_lens, input_len, P: int, prompt_ids, gamma, branches, max_ngram, min_ngram,
+                           max_gen_len, eos_id, sampling, penalties, prompt_state, logprobs, first_logprobs, stop, stop_table):
+        """State of the lookup loop with ``branches >= 2``: ``begin_tree_decode``'s without anything that belongs to a draft
+        layer -- ``all_spec`` / ``tree_mask`` of the static level-major tree (Fn = 1 + branches * gamma nodes), ``acc_pad``
+        [bsz, gamma + 1], ``a``, ``emitted_dev``, int32 ``cache_lens``, R = Fn - 1 + gamma + 1 verification rows -- and the
+        drafter's ``info`` / ``hist`` / ``hist_nb`` / ``won``.  ``output_ids`` (filled and EOS-tested as the tree loop's) is
+        max_gen_len + gamma + 1 columns wide: under the tree loop's rule -- stop when ``emitted + gamma + 2`` exceeds the width
+        -- the loop does not end before max_gen_len columns are written, and a round's gamma + 1 tokens always fit."""
+        bsz = first_token.shape[0]
+        dev = first_token.device
+        Fn = 1 + branches * gamma
+        R = Fn - 1 + gamma + 1
+        width = max_gen_len + gamma + 1
+        st = _DecodeState(gamma=gamma, branches=branches, max_ngram=max_ngram, min_ngram=min_ngram, Fn=Fn, R=R, P=P, dev=dev,
+                          bsz=bsz, sampling=sampling, max_gen_len=max_gen_len, rounds=0)
+        st.prompt_ids = prompt_ids.to(device=dev, dtype=torch.int64)
+        if st.prompt_ids.stride(-1) != 1:
+            st.prompt_ids = st.prompt_ids.contiguous()
+        st.input_len = input_len
+        st.input_len_i32 = input_len.to(device=dev, dtype=torch.int32).view(bsz).contiguous()
+        self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
+        self._begin_logprobs(st, logprobs, bsz, width, dev, first_logprobs)
+        st.fill = self._tree_output_fill(eos_id)
+        st.output_ids = torch.full((bsz, width), st.fill, dtype=torch.int64, device=dev)
+        st.spec_mask = torch.zeros((bsz, width), dtype=torch.int64, device=dev)
+        st.output_ids[:, 0] = first_token
+        st.cache_lens = cache_lens.to(torch.int32).clone()     # the tree operators advance it in place
+        st.count, st.num = 0, 0
+        st.all_spec = torch.zeros((bsz, Fn), dtype=torch.int64, device=dev)
+        st.all_spec[:, 0] = first_token
+        st.tree_mask = torch.zeros((bsz, Fn, Fn), dtype=torch.int64, device=dev)
+        st.tree_mask[:, :, 0] = 1
+        st.logp_sum = torch.zeros((bsz, Fn), dtype=torch.float32, device=dev)   # (tree_commit resets it with the rest)
+        st.acc_pad = torch.zeros((bsz, gamma + 1), dtype=torch.int64, device=dev)
+        st.acc_pad[:, 0] = first_token
+        st.acc_ids = st.acc_pad[:, :1]
+        st.a = 1                              # host mirror of acc_num
+        st.emitted = 1                        # host mirror of emitted_dev: columns of output_ids written so far
+        st.emitted_dev = torch.ones((bsz,), dtype=torch.int32, device=dev)
+        st.info = torch.zeros((bsz, branches, 2), dtype=torch.int32, device=dev)
+        st.hist = torch.zeros((bsz, max_ngram + 1), dtype=torch.int64, device=dev)
+        st.hist_nb = torch.zeros((bsz, branches + 1), dtype=torch.int64, device=dev)
+        st.won = torch.zeros((bsz, branches), dtype=torch.int64, device=dev)
+        st.last_lookup = SimpleNamespace(hist=st.hist, info=st.info, branches=branches, hist_nb=st.hist_nb, won=st.won)
+        st.eos = self._stop_id(eos_id, "tree")
+        self._begin_stop(st, stop, bsz, dev, stop_table)
+        if st.stop is not None:                              # column 0; a hit ends the loop with its first round
+            self._stop_scan(st, st.emitted_dev, fill=st.fill)
+        st.use_graphs = bool(dev.type == "cuda" and bsz == 1 and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
+        st.replayer = GraphReplayer(self, lambda bound: (P + bound + R, P + bound + R), width, "lookup tree round")
+        return st
+
+    def _lookup_tree_device(self, st, a: int):
+        """The device work of one lookup round with ``branches >= 2`` (no host read inside; ``a``, the tokens the last round
+        accepted, is its only host-side parameter): the tree from the text, then the V and A halves of ``_round_device``,
+        operator for operator, without a draft cache to keep.  Returns state [bsz, 2] = (acc_num, EOS hit | 2 * stop hit)."""
+        Fn, gamma, R, B = st.Fn, st.gamma, st.R, st.branches
+        tree_mask, all_spec = st.tree_mask, st.all_spec
+        ops = self.ops
+        acc_ids = st.acc_pad[:, :a]
+        bound = self.model.layers[-1].self_attn.kv_len_hint or st.P + st.output_ids.size(1)
+        ops.ngram_tree_draft(st.prompt_ids, st.input_len_i32, st.output_ids, st.emitted_dev, bound, gamma, B, st.max_ngram,
+                             st.min_ngram, all_spec, tree_mask, info=st.info, hist=st.hist, hist_nb=st.hist_nb)
+        # ---- V: one R-row target pass over [a accepted | Fn - 1 tree nodes | pads]
+        veri_spec, position_ids, mask_bits = ops.tree_verify_inputs(acc_ids, a, all_spec, tree_mask, st.cache_lens, R)
+        hidden_states = self.model.forward(veri_spec, position_ids=position_ids, cache_lens=st.cache_lens,
+                                           exec_type="tree_decoding", tree_mask_bits=mask_bits).last_hidden_state
+        llm_logits = self.lm_head(hidden_states[:, a - 1:a + Fn - 1])
+        if st.penalties is not None:
+            llm_logits = ops.penalize_rows(llm_logits, st.token_state, st.penalties, all_spec[:, 1:], tree_mask[:, :, 1:],
+                                           bias=st.bias_table)
+        if st.stop is not None and st.stop.min_tokens > 0:
+            llm_logits = ops.stop_ban_rows(llm_logits, st.stop.table, base=st.emitted_dev, depth="tree", tree_mask=tree_mask)
+        all_llm_pred = self._target_tokens(llm_logits, st.sampling,
+                                           position_ids[:, a - 1:a + Fn - 1] if st.sampling is not None else None)
+        # ---- A: the deepest branch that verifies; no KV row moves (the next pass feeds the accepted tokens again)
+        acc_pad, acc_num_t, _, index_mapping = ops.tree_collapse(all_spec, all_llm_pred, tree_mask, st.cache_lens,
+                                                                 1 + B * (gamma - 1), gamma + 1, out_acc_ids=st.acc_pad)
+        if st.logprobs is not None:
+            lp = st.logprobs
+            ops.logprob_commit(ops.token_logprobs(llm_logits, all_llm_pred, lp.temperature, lp.top_n), lp, st.emitted_dev,
+                               num=acc_num_t, index_map=index_mapping)
+        state = ops.tree_commit(acc_pad, acc_num_t, st.output_ids, 0, st.eos, tree_mask, all_spec, st.logp_sum,
+                                target_lens=st.cache_lens, target_add=a, emitted_dev=st.emitted_dev)
+        if st.penalties is not None:
+            ops.token_state_add(st.token_state, acc_pad, num=acc_num_t)
+        if st.stop is not None:
+            self._stop_scan(st, st.emitted_dev, num=acc_num_t, fill=st.fill, state=state)
+        # the branch of the deepest accepted node (node = 1 + (d-1) * B + j), where a draft token was accepted at all
+        n = acc_num_t.view(-1, 1).to(torch.int64)
+        last = index_mapping.gather(1, (n - 1).clamp(min=0))
+        st.won.scatter_add_(1, (last - 1).clamp(min=0) % B, n.ge(2).to(torch.int64))
+        return state
+
+    def _lookup_tree_round(self, st) -> bool:
+        """``lookup_round`` with ``branches >= 2``: the host side of ``tree_round`` -- one HIP graph per ``a`` and tier after
+        GRAPH_AFTER eager rounds, ONE host read -- around ``_lookup_tree_device``."""
+        a = st.a
+        state = None
+        if st.use_graphs and not st.replayer.disabled and st.rounds >= self.GRAPH_AFTER:
+            state = self._replay_round(st, a, partial(self._lookup_tree_device, st, a))
+        if state is None:
+            bound = st.P + st.emitted + st.R
+            self._set_hints(bound, bound)
+            state = self._lookup_tree_device(st, a)
+        st.rounds += 1
+        state = state.tolist()                                        # the round's ONE host read
+        a, hit = state[0][0], any(row[1] for row in state)
+        st.stopped = any(row[1] & 2 for row in state)
+        st.acc_ids = st.acc_pad[:, :a]
+        st.a = a
+        st.emitted += a
+        st.count += a - 1
+        st.num += st.bsz
+        if st.emitted + st.gamma + 2 > st.output_ids.size(1):
             return False
         return not hit
 

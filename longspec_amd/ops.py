@@ -17,6 +17,7 @@ One function per reference seam of the draft-then-verify round:
                          row from that row's own history, and the [batch, vocab] state they read (penalties=; no counterpart)
   ngram_draft            the drafter of prompt-lookup speculation: the continuation of the most recent earlier occurrence of
                          the text's last tokens (lookup_generate; no counterpart)
+  ngram_tree_draft       its tree drafter: up to `branches` distinct continuations as a level-major tree (lookup_generate(branches=))
   token_logprobs / logprob_commit   log-prob of every emitted token under the distribution it was taken from and the row's
                          top-n alternatives; the accepted rows' results -> the tokens' output columns (logprobs=; no counterpart)
   tree_commit / tree_commit_stochastic   end of a round at temperature 0 / > 0  llama_glide.py:1093-1121
@@ -109,7 +110,7 @@ _gemm_ws = _ZeroedWorkspace()
 def workspace_tensors():
     """The scratch buffers currently handed out (a captured HIP graph keeps them alive: it holds their addresses)."""
     return (list(_ws._buf.values()) + list(_gemm_ws._buf.values()) + list(_sample_ws._buf.values())
-            + list(_logprob_ws._buf.values()) + list(_ngram_ws._buf.values()))
+            + list(_logprob_ws._buf.values()) + list(_ngram_ws._buf.values()) + list(_ngram_tree_ws._buf.values()))
 
 
 _linear_need = {}            # (shape key) -> workspace bytes of the launch plan
@@ -685,6 +686,62 @@ def ngram_draft(prompt_ids: torch.Tensor, input_len: torch.Tensor, output_ids: t
                                 _len_i32(cache_lens, b, "cache_lens"), b, int(len_bound), gamma, max_ngram, min_ngram,
                                 spec_buffer.data_ptr(), info.data_ptr(), hist.data_ptr() if hist is not None else None,
                                 ws.data_ptr(), ws.numel(), _stream()), "ls_ngram_draft")
+    return info
+
+
+_ngram_tree_ws = _Workspace()     # (its records are LS_NGRAM_TOP times ngram_draft's: a buffer of its own)
+NGRAM_TOP = 8              # candidates the tree drafter walks (LS_NGRAM_TOP)
+
+
+def ngram_tree_draft(prompt_ids: torch.Tensor, input_len: torch.Tensor, output_ids: torch.Tensor, written: torch.Tensor,
+                     len_bound: int, gamma: int, branches: int, max_ngram: int, min_ngram: int, all_spec: torch.Tensor,
+                     tree_mask: torch.Tensor, info: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None,
+                     hist_nb: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The tree drafter of prompt-lookup speculation (``ls_ngram_tree_draft``, two launches; the definition is
+    ``longspec_amd/lookup.py``).  The text of row z is ``prompt_ids[z, :input_len[z]] ++ output_ids[z, :written[z]]``
+    (``written`` int32 [b] on the device: the tree round's ``emitted_dev``).  Up to ``branches`` distinct continuations of the
+    ``NGRAM_TOP`` best candidates go to ``all_spec[:, 1:]`` (contiguous int64 [b, F], F = 1 + branches * gamma, node
+    1 + (d-1) * branches + j = depth d of branch j; column 0 is kept) and the rows 1.. of ``tree_mask`` (contiguous int64
+    [b, F, F]; row 0 is kept) are written in full.  ``hist[z, n of slot 0] += 1`` (int64 [b, max_ngram + 1], optional),
+    ``hist_nb[z, nb] += 1`` (int64 [b, branches + 1], optional).  ``len_bound``: a HOST-side upper bound of the text lengths.
+    Returns ``info`` int32 [b, branches, 2] = (n, e) per slot, (0, -1) for the slots that copy slot 0."""
+    _dev(prompt_ids, input_len, output_ids, written, all_spec, tree_mask, info, hist, hist_nb)
+    for t, name in ((prompt_ids, "prompt_ids"), (output_ids, "output_ids")):
+        if t.dtype != torch.int64 or t.dim() != 2 or t.stride(1) != 1:
+            raise TypeError(f"ngram_tree_draft: {name} must be int64 [b, columns] with contiguous rows")
+    b = output_ids.shape[0]
+    if prompt_ids.shape[0] != b or (b > 1 and (prompt_ids.stride(0) < prompt_ids.shape[1] or output_ids.stride(0) < output_ids.shape[1])):
+        raise ValueError("ngram_tree_draft: prompt_ids and output_ids must have one row per batch row, rows apart")
+    if not (1 <= gamma <= NGRAM_MAX_GAMMA and 1 <= branches <= NGRAM_TOP and 1 <= max_ngram <= NGRAM_MAX_N
+            and 1 <= min_ngram <= max_ngram):
+        raise ValueError(f"ngram_tree_draft: gamma={gamma} (1..{NGRAM_MAX_GAMMA}), branches={branches} (1..{NGRAM_TOP}), "
+                         f"max_ngram={max_ngram} (1..{NGRAM_MAX_N}), min_ngram={min_ngram} (1..max_ngram)")
+    Fn = 1 + branches * gamma
+    if all_spec.dtype != torch.int64 or tuple(all_spec.shape) != (b, Fn) or not all_spec.is_contiguous():
+        raise TypeError(f"ngram_tree_draft: all_spec must be a contiguous int64 [{b}, {Fn}] tensor")
+    if tree_mask.dtype != torch.int64 or tuple(tree_mask.shape) != (b, Fn, Fn) or not tree_mask.is_contiguous():
+        raise TypeError(f"ngram_tree_draft: tree_mask must be a contiguous int64 [{b}, {Fn}, {Fn}] tensor")
+    if int(len_bound) < 1:
+        raise ValueError(f"ngram_tree_draft: len_bound={len_bound}")
+    dev = output_ids.device
+    if info is None:
+        info = torch.empty((b, branches, 2), dtype=torch.int32, device=dev)
+    elif info.dtype != torch.int32 or tuple(info.shape) != (b, branches, 2) or not info.is_contiguous():
+        raise TypeError(f"ngram_tree_draft: info must be a contiguous int32 [{b}, {branches}, 2] tensor")
+    for t, name, cols in ((hist, "hist", max_ngram + 1), (hist_nb, "hist_nb", branches + 1)):
+        if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != (b, cols) or not t.is_contiguous()):
+            raise TypeError(f"ngram_tree_draft: {name} must be a contiguous int64 [{b}, {cols}] tensor")
+    lib = _C.load()
+    need = lib.ls_ngram_tree_workspace_bytes(b, int(len_bound))
+    ws = _ngram_tree_ws.get(dev, max(need, 1))
+    _C.check(lib.ls_ngram_tree_draft(prompt_ids.data_ptr(), max(prompt_ids.stride(0), prompt_ids.shape[1]), prompt_ids.shape[1],
+                                     _len_i32(input_len, b, "input_len"), output_ids.data_ptr(),
+                                     max(output_ids.stride(0), output_ids.shape[1]), output_ids.shape[1],
+                                     _len_i32(written, b, "written"), b, int(len_bound), gamma, branches, max_ngram, min_ngram,
+                                     all_spec.data_ptr(), tree_mask.data_ptr(), info.data_ptr(),
+                                     hist.data_ptr() if hist is not None else None,
+                                     hist_nb.data_ptr() if hist_nb is not None else None, ws.data_ptr(), ws.numel(), _stream()),
+             "ls_ngram_tree_draft")
     return info
 
 
