@@ -447,6 +447,38 @@ int ls_stop_ban_rows(void* logits, int b, int rows, int vocab, int dtype, int64_
                      int table_words, const int32_t* base, const int32_t* base_sub, int base_add, int depth_mode,
                      const int64_t* mask, int64_t mask_stride_b, int64_t mask_stride_r, int mask_cols, void* stream);
 
+/* Banned sequences and no-repeat n-grams on the target's logits (ban=; csrc/ban.hip; no counterpart in the reference).
+ * table: int32 [LS_BAN_TABLE_WORDS] on the device -- [0] n_seqs (0..64), [1] n = no_repeat_ngram (0 = off, 1..16), [2] reserved,
+ * [3] the word count, [4:69] offsets of the sequences into the token area, [69:1093] their tokens back to back (1..16 each, -1
+ * padded).  Counts, n and offsets are clamped to this layout on the device before they index anything.
+ *
+ * ls_ban_rows: 16-bit logits [b, rows, vocab] (strides in elements, unit column stride, rows must not overlap), IN PLACE, one
+ * launch.  The text of row r of batch z is t = output_ids[z, :w] ++ path(r), m tokens: w = (base ? base[z] : 0) - (base_sub ?
+ * base_sub[z] : 0) + base_add clamped to 0..width (output_ids int64 [b, width], row stride out_stride_b; NULL with width 0: no
+ * columns), path(r) = extra_ids[z, c] for the c < n_extra with extra_mask[z, r, c] != 0, IN INCREASING c (extra_ids int64, row
+ * stride ids_stride_b; extra_mask int64, strides mask_stride_b -- 0: one mask for the batch -- and mask_stride_r, unit column
+ * stride; n_extra 0..LS_BAN_MAX_EXTRA).  Ids are compared as 64-bit integers, whatever their value.  Forbidden in row (z, r):
+ *   - s[L-1] of every listed sequence s of length L with L - 1 <= m and t[m-L+1 .. m-1] == s[0 .. L-2]  (L = 1: always);
+ *   - with n >= 1 and m >= n - 1: t[j] for every j in [n-1, m-1] with t[j-n+1 .. j-1] == t[m-n+1 .. m-1]  (n = 1: all of t).
+ * A forbidden id inside [0, vocab) gets the type's -inf pattern (0xfc00 / 0xff80) by a plain 16-bit store -- two lanes that hit
+ * one address store the same value --; every other element keeps its bits; ids outside [0, vocab) are never written.  Nothing
+ * in front of column 0 or at column w and beyond is read.  Grid (ceil(rows / 4) + ceil(width / LS_BAN_CHUNK) * ceil(rows / 32), b)
+ * workgroups of 256: a path workgroup takes one row per wave, assembles its ordered path in LDS and tests the sequences and the
+ * positions j >= w; a chunk workgroup reads the text columns [k * LS_BAN_CHUNK - 16, (k + 1) * LS_BAN_CHUNK) once into LDS and tests
+ * its positions j < w against the last n - 1 tokens of each of its 32 rows (k * LS_BAN_CHUNK >= w, or n = 0: it returns at
+ * once).  The grid depends on host-side shapes only: nothing is read back, safe inside a replayed graph.  Exact; no workspace,
+ * no atomics, no floating point.  LS_ERR_INVALID_ARG, before any launch: null logits / table, a dtype that is not 16-bit, b or
+ * rows outside 1..65535, vocab < 1, stride_r < vocab, table_words != LS_BAN_TABLE_WORDS, width outside 0..2^23 or without
+ * output_ids, out_stride_b < width, n_extra outside 0..LS_BAN_MAX_EXTRA (128: a verification pass has at most 80 rows) or without
+ * its two tensors. */
+#define LS_BAN_TABLE_WORDS 1093
+#define LS_BAN_CHUNK 1024
+#define LS_BAN_MAX_EXTRA 128
+int ls_ban_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t stride_b, int64_t stride_r, const int32_t* table,
+                int table_words, const int64_t* output_ids, int64_t out_stride_b, int width, const int32_t* base,
+                const int32_t* base_sub, int base_add, const int64_t* extra_ids, int64_t ids_stride_b, const int64_t* extra_mask,
+                int64_t mask_stride_b, int64_t mask_stride_r, int n_extra, void* stream);
+
 /* The drafter of prompt-lookup (n-gram) speculation (lookup_generate; csrc/lookup.hip; no counterpart in the reference, whose
  * every loop needs a trained draft layer).  The text of batch row z is T = prompt_ids[z, :il] ++ output_ids[z, :w], il =
  * input_len[z] clamped to 0..prompt_cols, w = cache_lens[z] - input_len[z] + 1 clamped to 0..out_cap (the columns written so far,

@@ -10,3 +10,4 @@ from .sampling import Sampling  # noqa: E402,F401
 from .penalties import Penalties  # noqa: E402,F401
 from .logprobs import Logprobs  # noqa: E402,F401
 from .stop import Stop  # noqa: E402,F401
+from .ban import Ban  # noqa: E402,F401

@@ -26,6 +26,7 @@ from .sampling import resolve as _resolve_sampling
 from .penalties import resolve as _resolve_penalties
 from .logprobs import new_buffers as _logprob_buffers, resolve as _resolve_logprobs
 from .stop import new_state as _stop_state, resolve as _resolve_stop, result_of as _stop_result
+from .ban import resolve as _resolve_ban
 from .lookup import check as _lookup_check
 from .llama import (DecodeLinear, LlamaForCausalLM, LlamaMLP, LlamaRMSNorm, chunked_causal_prefill,
                     project_qkv, _default_ops)
@@ -421,6 +422,21 @@ class LlamaGlide(LlamaForCausalLM):
         st.stop_state = _stop_state(bsz, device)
         st.last_stop = _stop_result(st.stop_state)
 
+    def _begin_ban(self, st, ban, device, table=None):
+        """The ban part of a decode state: ``st.ban`` = None, or a namespace of ``cfg`` (the ``Ban``) and ``table`` (its int32
+        device table, ``table`` when the caller has built it already, for the first token) -- put there now, nothing is copied
+        inside a graph capture.  The ban needs no state beyond ``st.output_ids``.  Refused under a vocabulary-parallel shard: no
+        rank holds a whole row of logits there."""
+        st.ban = None
+        if ban is None:
+            return
+        sh = self.model.layers[-1].self_attn.shard
+        if sh is not None and sh.vocab_parallel:
+            raise ValueError("ban= is not available with a vocabulary-parallel shard")
+        if table is None:
+            table = ban.table(self.lm_head.out_features, device)
+        st.ban = SimpleNamespace(cfg=ban, table=table)
+
     def _stop_scan(self, st, written, written_sub=None, written_add=0, num=None, fill=0, state=None):
         """``ops.stop_scan`` on a decode state: the columns this round (``num`` per row; None: one) wrote to ``st.output_ids``,
         erasing ``st.spec_mask`` and ``st.logprobs`` along with it where the state has them."""
@@ -428,15 +444,18 @@ class LlamaGlide(LlamaForCausalLM):
                            num=num, fill=fill, state=state, spec_mask=getattr(st, "spec_mask", None), logprobs=st.logprobs)
 
     def _first_token(self, logits, sampling, input_len, penalties=None, prompt_state=None, logprobs=None, stop=None,
-                     stop_table=None):
+                     stop_table=None, ban_table=None):
         """The prefill's token from ``logits`` [bsz, V] of prompt row ``input_len - 1``; under ``penalties`` the history of
         that row is the prompt alone (``prompt_state``: ``_token_state`` of the prompt); under a ``stop`` with ``min_tokens > 0``
-        the stop ids of ``stop_table`` are banned from it (column 0).  Returns (token, its log-prob rows
+        the stop ids of ``stop_table`` are banned from it (column 0); under ``ban_table`` (``Ban.table``) the one-token sequences
+        are (its text is empty).  Returns (token, its log-prob rows
         (``ops.token_logprobs``) under ``logprobs``, else None)."""
         if penalties is not None:
             logits = self.ops.penalize_rows(logits, prompt_state, penalties)
         if stop is not None and stop.min_tokens > 0:
             logits = self.ops.stop_ban_rows(logits, stop_table)
+        if ban_table is not None:
+            logits = self.ops.ban_rows(logits, ban_table, None)
         if sampling is None:
             token = logits.argmax(dim=-1)
         else:
@@ -469,7 +488,7 @@ class LlamaGlide(LlamaForCausalLM):
 
     @torch.inference_mode()
     def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645, sampling=None,
-                         penalties=None, logprobs=None, stop=None):                                                # :552-585
+                         penalties=None, logprobs=None, stop=None, ban=None):                                      # :552-585
         """``sampling`` (``longspec_amd.Sampling``): every token is drawn from the target's filtered distribution instead of
         taken as its arg-max -- the denominator of a sampled speculative run, and with the same seed the same text.
         ``penalties`` (``longspec_amd.Penalties``): the logits of every step are penalised from the prompt and the text so far.
@@ -480,13 +499,17 @@ class LlamaGlide(LlamaForCausalLM):
         back to 0, the loop ends when every row has stopped (tested where the EOS test is, every 16th step) and the elapsed
         time is cut back to the step of the last row's stop.  The result is ``self.last_stop`` (None without it).  The built-in
         EOS test runs alongside, unchanged.  ``num``, the KV lengths and the penalty state are not rolled back: they describe
-        the steps that ran, ``last_stop.length`` is the authority on the text."""
+        the steps that ran, ``last_stop.length`` is the authority on the text.
+        ``ban`` (``longspec_amd.Ban``): banned sequences and no-repeat n-grams (``ban.py``): the tokens the text so far forbids
+        are -inf in every step's logits, behind the penalties and in front of the arg-max or draw and the log-probs."""
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, None, use_env=True)
         pen = _resolve_penalties(penalties, None, use_env=True)
         lpc = _resolve_logprobs(logprobs, None, use_env=True)
         stp = _resolve_stop(stop, None, use_env=True)
         stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
+        bn = _resolve_ban(ban, None, use_env=True)
+        btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
         self._clear_shard()
         bsz = input_ids.size(0)
         output_ids = input_ids.new_zeros((bsz, max_gen_len))
@@ -499,7 +522,7 @@ class LlamaGlide(LlamaForCausalLM):
         rows = torch.arange(bsz, device=input_ids.device)
         pstate = self._token_state(bsz, input_ids.device, input_ids, input_len) if pen is not None else None
         output_ids[:, 0], first_lp = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), sampling, input_len,
-                                                       pen, pstate, lpc, stp, stab)
+                                                       pen, pstate, lpc, stp, stab, btab)
         cache_lens += input_len.int()
         num = 0
         eos = self._stop_id(eos_id, "vanilla")
@@ -512,7 +535,7 @@ class LlamaGlide(LlamaForCausalLM):
             ev0.record()
         vs = self.begin_vanilla_decode(output_ids, cache_lens, input_len.int(), P, sampling=sampling, penalties=penalties,
                                        prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp,
-                                       stop=stop, stop_table=stab)
+                                       stop=stop, stop_table=stab, ban=ban, ban_table=btab)
         self.last_logprobs = vs.logprobs
         self.last_stop = vs.last_stop
         for step in range(1, max_gen_len):
@@ -554,7 +577,8 @@ class LlamaGlide(LlamaForCausalLM):
 
     # ------------------------------------------------------------------------------------------
     def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int, sampling=None, penalties=None,
-                             prompt_ids=None, prompt_state=None, logprobs=None, first_logprobs=None, stop=None, stop_table=None):
+                             prompt_ids=None, prompt_state=None, logprobs=None, first_logprobs=None, stop=None, stop_table=None,
+                             ban=None, ban_table=None):
         """State of the vanilla loop (``llama_glide.py:566-583``): ``output_ids`` [bsz, max_gen] with the first
         token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32.  ``sampling``:
         draw instead of arg-max (None: the process-wide default LONGSPEC_SAMPLING, else greedy).  ``penalties``: penalise
@@ -565,17 +589,20 @@ class LlamaGlide(LlamaForCausalLM):
         tests its column against the stops (``stop.py``; None: the process-wide default LONGSPEC_STOP, else none;
         ``stop_table``: its device table, already built) and keeps ``vs.stop_state`` / ``vs.last_stop``; column 0 is tested
         here.  A row that has stopped keeps decoding with the batch, and every step erases what it wrote; KV lengths and the
-        penalty state are not rolled back."""
+        penalty state are not rolled back.  ``ban``: every step's logits carry -inf where the text so far forbids a token
+        (``ban.py``; None: the process-wide default LONGSPEC_BAN, else none; ``ban_table``: its device table, already built)."""
         dev = output_ids.device
         sampling = _resolve_sampling(sampling, None, use_env=True)
         penalties = _resolve_penalties(penalties, None, use_env=True)
         logprobs = _resolve_logprobs(logprobs, None, use_env=True)
         stop = _resolve_stop(stop, None, use_env=True)
+        ban = _resolve_ban(ban, None, use_env=True)
         vs = _DecodeState(output_ids=output_ids, cache_lens=cache_lens, input_len=input_len, P=prompt_bound, step=0,
                           rows=torch.arange(output_ids.size(0), device=dev), sampling=sampling, penalties=penalties)
         self._begin_penalties(vs, penalties, output_ids.size(0), dev, prompt_ids, input_len, output_ids[:, 0], prompt_state)
         self._begin_logprobs(vs, logprobs, output_ids.size(0), output_ids.size(1), dev, first_logprobs)
         self._begin_stop(vs, stop, output_ids.size(0), dev, stop_table)
+        self._begin_ban(vs, ban, dev, ban_table)
         if vs.stop is not None:
             self._stop_scan(vs, cache_lens, input_len, 1)
         vs.streams = torch.arange(output_ids.size(0), device=dev, dtype=torch.int32) if sampling is not None else None
@@ -595,6 +622,8 @@ class LlamaGlide(LlamaForCausalLM):
             logits = self.ops.penalize_rows(logits, vs.token_state, vs.penalties, bias=vs.bias_table)
         if vs.stop is not None and vs.stop.min_tokens > 0:    # the row predicts column cl - il + 1
             logits = self.ops.stop_ban_rows(logits, vs.stop.table, base=cl, base_sub=il, base_add=1)
+        if vs.ban is not None:                                # the text so far: columns 0 .. cl - il
+            logits = self.ops.ban_rows(logits, vs.ban.table, out, base=cl, base_sub=il, base_add=1)
         llm_output = self._target_tokens(logits, vs.sampling, cl, vs.streams)
         cl += 1
         out[rows, (cl - il).long()] = llm_output.view(-1)
@@ -631,18 +660,18 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def spec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                      sampling=None, penalties=None, logprobs=None, stop=None):                                    # :621-774
+                      sampling=None, penalties=None, logprobs=None, stop=None, ban=None):                          # :621-774
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="glide",
-                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop)
+                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop, ban=ban)
 
     @torch.inference_mode()
     def magicdec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                          sampling=None, penalties=None, logprobs=None, stop=None):                                # :776-913
+                          sampling=None, penalties=None, logprobs=None, stop=None, ban=None):                      # :776-913
         """The MagicDec baseline of the reference's harness (``--method magicdec``): chain speculation where the
         drafter is the TARGET itself attending to a StreamingLLM cache (32 sink rows + the last 1024 prompt rows +
         what it generates), verified exactly like ``spec_generate``.  Same return tuple."""
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="magicdec",
-                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop)
+                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop, ban=ban)
 
     @torch.inference_mode()
     def vanilla_torch_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645):                      # :587-619
@@ -653,13 +682,15 @@ class LlamaGlide(LlamaForCausalLM):
         return self.vanilla_generate(input_ids, prompt_length, max_gen_len=max_gen_len, eos_id=eos_id)
 
     def _chain_generate(self, input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter, sampling=None,
-                        penalties=None, logprobs=None, stop=None):
+                        penalties=None, logprobs=None, stop=None, ban=None):
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         pen = _resolve_penalties(penalties, temperature, use_env=True)
         lpc = _resolve_logprobs(logprobs, temperature, use_env=True)
         stp = _resolve_stop(stop, temperature, use_env=True)
         stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
+        bn = _resolve_ban(ban, temperature, use_env=True)
+        btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
         magic = drafter == "magicdec"       # (temperature > 0: the same rejection block in both loops, :715-736 = :854-875)
         self._clear_shard()
         bsz = input_ids.size(0)
@@ -682,10 +713,11 @@ class LlamaGlide(LlamaForCausalLM):
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=cache_lens.clone(), llm_kv_len=cache_lens.clone(), exec_type="prefill")
         pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
-        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab)
+        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab, btab)
         st = self.begin_chain_decode(first, cache_lens, input_len, P, gamma, max_gen_len, eos_id, temperature, drafter,
                                      first_logits=logits, sampling=sampling, penalties=penalties, prompt_ids=input_ids,
-                                     prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp, stop=stop, stop_table=stab)
+                                     prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp, stop=stop, stop_table=stab,
+                                     ban=ban, ban_table=btab)
         self.last_logprobs = st.logprobs
         self.last_stop = st.last_stop
         _sync(input_ids)
@@ -699,7 +731,8 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_chain_decode(self, first_token, cache_lens, input_len, prompt_bound: int, gamma=4, max_gen_len=64, eos_id=151645,
                            temperature=0.0, drafter="glide", first_logits=None, sampling=None, penalties=None, prompt_ids=None,
-                           prompt_state=None, logprobs=None, first_logprobs=None, stop=None, stop_table=None):
+                           prompt_state=None, logprobs=None, first_logprobs=None, stop=None, stop_table=None, ban=None,
+                           ban_table=None):
         """State of the chain-speculation loop right after the prefills (``llama_glide.py:641-668``): ``first_token`` [bsz]
         = the target's first generated token, ``cache_lens`` [bsz] int32 = valid rows of every cache (the draft's included),
         ``input_len`` [bsz] = prompt length, ``prompt_bound`` = host-side bound of it.  Also the entry point of benchmarks
@@ -713,21 +746,26 @@ class LlamaGlide(LlamaForCausalLM):
         default LONGSPEC_STOP, else none; ``stop_table``: its device table, already built) inside the round, in front of its one
         host read; a match ends the loop with that round, the columns of ``output_ids`` / ``spec_mask`` / ``st.logprobs`` behind
         it go back to their fill and ``st.last_stop`` holds (length, which, match_start).  KV lengths, ``st.token_state`` and the
-        host counters ``count`` / ``num`` / ``emitted`` are not rolled back: a stopped state is final."""
+        host counters ``count`` / ``num`` / ``emitted`` are not rolled back: a stopped state is final.  ``ban``: verification row
+        i carries -inf where the text so far plus the i draft tokens it follows forbid a token (``ban.py``; None at temperature
+        0: the process-wide default LONGSPEC_BAN, else none; ``ban_table``: its device table, already built); the drafter stays
+        unbanned."""
         bsz = first_token.size(0)
         dev = first_token.device
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         penalties = _resolve_penalties(penalties, temperature, use_env=True)
         logprobs = _resolve_logprobs(logprobs, temperature, use_env=True)
         stop = _resolve_stop(stop, temperature, use_env=True)
+        ban = _resolve_ban(ban, temperature, use_env=True)
         if drafter != "magicdec":
             self._head_of_draft_passes()                # the draft passes' head and its pack exist before the first round
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
                              max_gen_len=max_gen_len, count=0, num=0, emitted=1, double_flag=False, sampling=sampling)
         st.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if sampling is not None else None
         self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
+        self._begin_ban(st, ban, dev, ban_table)
         st.chain_mask = None
-        if penalties is not None:
+        if penalties is not None or st.ban is not None:
             # verification row i follows the draft tokens spec_buffer[:, 1 : i + 1]
             st.chain_mask = torch.ones((gamma + 1, gamma), dtype=torch.int64, device=dev).tril(-1)
         self._begin_logprobs(st, logprobs, bsz, max_gen_len + gamma, dev, first_logprobs)
@@ -815,6 +853,10 @@ class LlamaGlide(LlamaForCausalLM):
         if st.stop is not None and st.stop.min_tokens > 0:   # row i predicts column cache_lens - input_len + 1 + i
             llm_verify_logits = self.ops.stop_ban_rows(llm_verify_logits, st.stop.table, base=cache_lens, base_sub=st.input_len_i32,
                                                        base_add=1, depth="row")
+        if st.ban is not None:                               # row i: columns 0 .. cache_lens - input_len, then i draft tokens
+            llm_verify_logits = self.ops.ban_rows(llm_verify_logits, st.ban.table, output_ids, base=cache_lens,
+                                                  base_sub=st.input_len_i32, base_add=1, extra_ids=spec_buffer[:, 1:],
+                                                  extra_mask=st.chain_mask)
         # (sampling: verification row i was rotated to position cache_lens + i, models' forward :571-577)
         llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
                                                 cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
@@ -852,13 +894,13 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def lookup_generate(self, input_ids, prompt_length, gamma=7, max_ngram=3, min_ngram=1, max_gen_len=64, eos_id=151645,
-                        sampling=None, penalties=None, logprobs=None, stop=None, branches=1):
+                        sampling=None, penalties=None, logprobs=None, stop=None, branches=1, ban=None):
         """Prompt-lookup (n-gram) speculation (no counterpart in the reference): chain speculation whose drafter is the text
         itself -- the ``gamma`` tokens that followed the most recent earlier occurrence of the last ``min_ngram .. max_ngram``
         tokens of prompt + output (``lookup.py``) -- verified exactly like ``spec_generate``.  No draft weights, no draft KV,
         no draft prefill and no draft pass: the glide layer is never called, so a model without a draft checkpoint can use
         it.  A round is one ``ops.ngram_draft`` and one (gamma + 1)-row target pass.  Same return tuple as ``spec_generate``;
-        ``sampling`` / ``penalties`` / ``logprobs`` / ``stop`` act on the verification rows as they do there
+        ``sampling`` / ``penalties`` / ``logprobs`` / ``stop`` / ``ban`` act on the verification rows as they do there
         (``self.last_logprobs``, ``self.last_stop``); ``self.last_lookup`` holds ``hist`` [bsz, max_ngram + 1] int64 -- how many
         rounds matched at which length, [:, 0] = none -- and ``info`` [bsz, 2] int32 = (n, e) of the last round, both on the
         device.  There is no ``temperature=``: the reference's T > 0 rejection needs the draft logits a lookup does not have.
@@ -877,6 +919,8 @@ class LlamaGlide(LlamaForCausalLM):
         lpc = _resolve_logprobs(logprobs, None, use_env=True)
         stp = _resolve_stop(stop, None, use_env=True)
         stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
+        bn = _resolve_ban(ban, None, use_env=True)
+        btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
         self._clear_shard()
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
@@ -890,10 +934,11 @@ class LlamaGlide(LlamaForCausalLM):
         logits = self.lm_head(hidden_states[rows, input_len - 1, :])
         cache_lens = input_ids.new_zeros((bsz)).int() + input_len.int()
         pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
-        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab)
+        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab, btab)
         st = self.begin_lookup_decode(first, cache_lens, input_len, P, input_ids, gamma, max_ngram, min_ngram, max_gen_len, eos_id,
                                       sampling=sampling, penalties=penalties, prompt_state=pstate, logprobs=logprobs,
-                                      first_logprobs=first_lp, stop=stop, stop_table=stab, branches=branches)
+                                      first_logprobs=first_lp, stop=stop, stop_table=stab, branches=branches, ban=ban,
+                                      ban_table=btab)
         self.last_logprobs = st.logprobs
         self.last_stop = st.last_stop
         self.last_lookup = st.last_lookup
@@ -908,7 +953,8 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_lookup_decode(self, first_token, cache_lens, input_len, prompt_bound: int, prompt_ids, gamma=7, max_ngram=3,
                             min_ngram=1, max_gen_len=64, eos_id=151645, sampling=None, penalties=None, prompt_state=None,
-                            logprobs=None, first_logprobs=None, stop=None, stop_table=None, branches=1):
+                            logprobs=None, first_logprobs=None, stop=None, stop_table=None, branches=1, ban=None,
+                            ban_table=None):
         """State of the prompt-lookup loop right after the target's prefill: the arguments of ``begin_chain_decode`` that have
         a meaning without a drafter, plus ``prompt_ids`` [bsz, P] -- here not optional: ``prompt_ids[z, :input_len[z]]`` is the
         front of the text the drafter searches (and, under ``penalties``, the source of the prompt flags).  Also the entry point
@@ -922,10 +968,11 @@ class LlamaGlide(LlamaForCausalLM):
         penalties = _resolve_penalties(penalties, None, use_env=True)
         logprobs = _resolve_logprobs(logprobs, None, use_env=True)
         stop = _resolve_stop(stop, None, use_env=True)
+        ban = _resolve_ban(ban, None, use_env=True)
         if branches > 1:
             return self._begin_lookup_tree(first_token, cache_lens, input_len, int(prompt_bound), prompt_ids, gamma, branches,
                                            max_ngram, min_ngram, max_gen_len, eos_id, sampling, penalties, prompt_state, logprobs,
-                                           first_logprobs, stop, stop_table)
+                                           first_logprobs, stop, stop_table, ban, ban_table)
         st = _DecodeState(gamma=gamma, max_ngram=max_ngram, min_ngram=min_ngram, bsz=bsz, P=int(prompt_bound),
                           max_gen_len=max_gen_len, count=0, num=0, emitted=1, rounds=0, sampling=sampling)
         st.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if sampling is not None else None
@@ -933,8 +980,9 @@ class LlamaGlide(LlamaForCausalLM):
         if st.prompt_ids.stride(-1) != 1:
             st.prompt_ids = st.prompt_ids.contiguous()
         self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
+        self._begin_ban(st, ban, dev, ban_table)
         st.chain_mask = None
-        if penalties is not None:
+        if penalties is not None or st.ban is not None:
             # verification row i follows the draft tokens spec_buffer[:, 1 : i + 1]
             st.chain_mask = torch.ones((gamma + 1, gamma), dtype=torch.int64, device=dev).tril(-1)
         self._begin_logprobs(st, logprobs, bsz, max_gen_len + gamma, dev, first_logprobs)
@@ -979,6 +1027,10 @@ class LlamaGlide(LlamaForCausalLM):
         if st.stop is not None and st.stop.min_tokens > 0:   # row i predicts column cache_lens - input_len + 1 + i
             llm_verify_logits = self.ops.stop_ban_rows(llm_verify_logits, st.stop.table, base=cache_lens, base_sub=st.input_len_i32,
                                                        base_add=1, depth="row")
+        if st.ban is not None:                               # row i: columns 0 .. cache_lens - input_len, then i draft tokens
+            llm_verify_logits = self.ops.ban_rows(llm_verify_logits, st.ban.table, output_ids, base=cache_lens,
+                                                  base_sub=st.input_len_i32, base_add=1, extra_ids=spec_buffer[:, 1:],
+                                                  extra_mask=st.chain_mask)
         # (sampling: verification row i was rotated to position cache_lens + i)
         llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
                                                 cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
@@ -1039,7 +1091,8 @@ class LlamaGlide(LlamaForCausalLM):
         return not hit
 
     def _begin_lookup_tree(self, first_token, cache_lens, input_len, P: int, prompt_ids, gamma, branches, max_ngram, min_ngram,
-                           max_gen_len, eos_id, sampling, penalties, prompt_state, logprobs, first_logprobs, stop, stop_table):
+                           max_gen_len, eos_id, sampling, penalties, prompt_state, logprobs, first_logprobs, stop, stop_table,
+                           ban=None, ban_table=None):
         """State of the lookup loop with ``branches >= 2``: ``begin_tree_decode``'s without anything that belongs to a draft
         layer -- ``all_spec`` / ``tree_mask`` of the static level-major tree (Fn = 1 + branches * gamma nodes), ``acc_pad``
         [bsz, gamma + 1], ``a``, ``emitted_dev``, int32 ``cache_lens``, R = Fn - 1 + gamma + 1 verification rows -- and the
@@ -1060,6 +1113,7 @@ class LlamaGlide(LlamaForCausalLM):
         st.input_len_i32 = input_len.to(device=dev, dtype=torch.int32).view(bsz).contiguous()
         self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
         self._begin_logprobs(st, logprobs, bsz, width, dev, first_logprobs)
+        self._begin_ban(st, ban, dev, ban_table)
         st.fill = self._tree_output_fill(eos_id)
         st.output_ids = torch.full((bsz, width), st.fill, dtype=torch.int64, device=dev)
         st.spec_mask = torch.zeros((bsz, width), dtype=torch.int64, device=dev)
@@ -1111,6 +1165,9 @@ class LlamaGlide(LlamaForCausalLM):
                                            bias=st.bias_table)
         if st.stop is not None and st.stop.min_tokens > 0:
             llm_logits = ops.stop_ban_rows(llm_logits, st.stop.table, base=st.emitted_dev, depth="tree", tree_mask=tree_mask)
+        if st.ban is not None:            # row j: the committed columns, then the nodes on its path (level-major: path order)
+            llm_logits = ops.ban_rows(llm_logits, st.ban.table, st.output_ids, base=st.emitted_dev, extra_ids=all_spec[:, 1:],
+                                      extra_mask=tree_mask[:, :, 1:])
         all_llm_pred = self._target_tokens(llm_logits, st.sampling,
                                            position_ids[:, a - 1:a + Fn - 1] if st.sampling is not None else None)
         # ---- A: the deepest branch that verifies; no KV row moves (the next pass feeds the accepted tokens again)
@@ -1160,7 +1217,7 @@ class LlamaGlide(LlamaForCausalLM):
     @torch.inference_mode()
     def tree_spec_generate(self, input_ids, prompt_length, tree_shape: Optional[List[int]] = None, max_gen_len=64,
                            eos_id=151645, temperature=0.0, shard=None, sampling=None, penalties=None,
-                           logprobs=None, stop=None):                                                         # :915-1126
+                           logprobs=None, stop=None, ban=None):                                               # :915-1126
         """``shard`` (``dist.KVShard``, every rank of the group calls with the same arguments): the prompt is prefilled
         and its KV kept sequence-sharded over the ranks (``_sharded_prefill``); decoding then runs replicated with one
         exchange per attention call.  Returns the same values on every rank.  ``sampling``: the verification pass draws
@@ -1170,7 +1227,9 @@ class LlamaGlide(LlamaForCausalLM):
         the emitted tokens and their top-n alternatives as ``self.last_logprobs`` (not with a vocabulary-parallel shard; under
         a sequence shard every rank computes the same values).  ``stop``: stop tokens, stop sequences and ``min_tokens``
         (``stop.py``), the result as ``self.last_stop``; the stop test reads ``output_ids`` only, so every rank of either shard
-        computes the same result -- ``min_tokens > 0`` alone is refused with a vocabulary-parallel shard."""
+        computes the same result -- ``min_tokens > 0`` alone is refused with a vocabulary-parallel shard.  ``ban``: banned
+        sequences and no-repeat n-grams on every verification row, from the committed text and the row's tree path (``ban.py``;
+        not with a vocabulary-parallel shard; under a sequence shard every rank computes the same rows)."""
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         pen = _resolve_penalties(penalties, temperature, use_env=True)
@@ -1185,6 +1244,10 @@ class LlamaGlide(LlamaForCausalLM):
             raise ValueError("penalties= is not available with a vocabulary-parallel shard")
         if lpc is not None and shard is not None and shard.vocab_parallel:
             raise ValueError("logprobs= is not available with a vocabulary-parallel shard")
+        bn = _resolve_ban(ban, temperature, use_env=True)
+        if bn is not None and shard is not None and shard.vocab_parallel:
+            raise ValueError("ban= is not available with a vocabulary-parallel shard")
+        btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
         dev = input_ids.device
@@ -1205,13 +1268,13 @@ class LlamaGlide(LlamaForCausalLM):
                 heads = max(self.config.num_attention_heads, self.glide.config.num_attention_heads)
                 shard.enable_peer_exchange(bsz * 128 * heads * 129, dev)
             first, first_lp = self._sharded_prefill(input_ids, input_len, position_ids, shard, sampling, pen, pstate, lpc, stp,
-                                                    stab)
+                                                    stab, btab)
         else:
             # prefill LLM (:954-960)
             self._set_hints(P, P)
             hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
             first, first_lp = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), sampling, input_len, pen,
-                                                pstate, lpc, stp, stab)
+                                                pstate, lpc, stp, stab, btab)
             # prefill glide (:968-975)
             hidden_states = self.model.embed_tokens(input_ids)
             position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
@@ -1219,7 +1282,7 @@ class LlamaGlide(LlamaForCausalLM):
                        cache_lens=lens.clone(), llm_kv_len=lens.clone(), exec_type="prefill")
         st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature, sampling=sampling,
                                     penalties=penalties, prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs,
-                                    first_logprobs=first_lp, stop=stop, stop_table=stab)
+                                    first_logprobs=first_lp, stop=stop, stop_table=stab, ban=ban, ban_table=btab)
         self.last_logprobs = st.logprobs
         self.last_stop = st.last_stop
         _sync(input_ids)
@@ -1239,7 +1302,7 @@ class LlamaGlide(LlamaForCausalLM):
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
     def _sharded_prefill(self, input_ids, input_len, position_ids, shard, sampling=None, penalties=None, prompt_state=None,
-                         logprobs=None, stop=None, stop_table=None):
+                         logprobs=None, stop=None, stop_table=None, ban_table=None):
         """Sequence-sharded prefill: rank r runs the target model on prompt rows [r*Ls, (r+1)*Ls) only
         (one all-gather of the layer's K/V rows per layer, ``LlamaAttention.sharded_prefill``) and keeps that slice of the
         KV; the tail rank computes the first token (and, under ``logprobs``, its log-prob rows) and broadcasts it.  The
@@ -1270,7 +1333,7 @@ class LlamaGlide(LlamaForCausalLM):
                         torch.zeros((bsz, 1, logprobs.top_n), dtype=torch.int64, device=dev))
         if shard.is_tail:
             first, first_lp = self._first_token(self.lm_head(hidden_states[:, hi - lo - 1, :]), sampling, input_len, penalties,
-                                                prompt_state, logprobs, stop, stop_table)
+                                                prompt_state, logprobs, stop, stop_table, ban_table)
         shard.broadcast_from_tail(first)
         for t in first_lp or ():
             if t.numel():
@@ -1281,7 +1344,7 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_tree_decode(self, first_token, cache_lens, prompt_bound: int, tree_shape=None, max_gen_len=64, eos_id=151645,
                           temperature=0.0, sampling=None, penalties=None, prompt_ids=None, prompt_state=None, logprobs=None,
-                          first_logprobs=None, stop=None, stop_table=None):
+                          first_logprobs=None, stop=None, stop_table=None, ban=None, ban_table=None):
         """State of the round loop right after the two prefills (``llama_glide.py:927-991``).
         ``first_token`` [bsz] = the target's first generated token, ``cache_lens`` [bsz] int32 = valid
         rows of every KV cache, ``prompt_bound`` = host-side bound of it.  Also the entry point of
@@ -1297,12 +1360,16 @@ class LlamaGlide(LlamaForCausalLM):
         device table, already built) inside the round and its graph, in front of the one host read; a match ends the loop with
         that round, the columns of ``output_ids`` / ``spec_mask`` / ``st.logprobs`` behind it go back to their fill and
         ``st.last_stop`` holds (length, which, match_start).  KV lengths, ``st.token_state`` and the host counters ``count`` /
-        ``num`` / ``emitted`` are not rolled back: a stopped state is final and ``last_stop.length`` is the authority."""
+        ``num`` / ``emitted`` are not rolled back: a stopped state is final and ``last_stop.length`` is the authority.  ``ban``:
+        verification row j carries -inf where the committed text plus the nodes on node j's path forbid a token (``ban.py``;
+        None at temperature 0: the process-wide default LONGSPEC_BAN, else none; ``ban_table``: its device table, already
+        built), inside the round and its graph; the draft passes stay unbanned."""
         dev = first_token.device
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         penalties = _resolve_penalties(penalties, temperature, use_env=True)
         logprobs = _resolve_logprobs(logprobs, temperature, use_env=True)
         stop = _resolve_stop(stop, temperature, use_env=True)
+        ban = _resolve_ban(ban, temperature, use_env=True)
         sh = self.model.layers[-1].self_attn.shard
         if sampling is not None and sh is not None and sh.vocab_parallel:
             raise ValueError("sampling= is not available with a vocabulary-parallel shard")
@@ -1318,6 +1385,7 @@ class LlamaGlide(LlamaForCausalLM):
         st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz, sampling=sampling)
         self._begin_penalties(st, penalties, bsz, dev, prompt_ids, cache_lens, first_token, prompt_state)
         self._begin_logprobs(st, logprobs, bsz, max_gen_len, dev, first_logprobs)
+        self._begin_ban(st, ban, dev, ban_table)
         st.output_ids = torch.full((bsz, max_gen_len), self._tree_output_fill(eos_id), dtype=torch.int64, device=dev)  # :937 (G8)
         st.spec_mask = torch.zeros((bsz, max_gen_len), dtype=torch.int64, device=dev)
         st.output_ids[:, 0] = first_token
@@ -1541,6 +1609,11 @@ class LlamaGlide(LlamaForCausalLM):
             if st.stop is not None and st.stop.min_tokens > 0:
                 # row j predicts column emitted + depth(j): the root the next column, a node its depth further on
                 llm_logits = ops.stop_ban_rows(llm_logits, st.stop.table, base=st.emitted_dev, depth="tree", tree_mask=tree_mask)
+            if st.ban is not None:
+                # row j's text: the emitted columns, then the nodes on its path -- tree_grow appends level by level, so
+                # increasing column is increasing depth
+                llm_logits = ops.ban_rows(llm_logits, st.ban.table, st.output_ids, base=st.emitted_dev, extra_ids=all_spec[:, 1:],
+                                          extra_mask=tree_mask[:, :, 1:])
             all_llm_pred = self._target_tokens(llm_logits, st.sampling,
                                                position_ids[:, a - 1:a + Fn - 1] if st.sampling is not None else None)
         # ---- A: accept / reject tree collapse + last-layer KV row move (:1104-1116); the accepted rows start at

@@ -20,6 +20,9 @@ One function per reference seam of the draft-then-verify round:
   ngram_tree_draft       its tree drafter: up to `branches` distinct continuations as a level-major tree (lookup_generate(branches=))
   token_logprobs / logprob_commit   log-prob of every emitted token under the distribution it was taken from and the row's
                          top-n alternatives; the accepted rows' results -> the tokens' output columns (logprobs=; no counterpart)
+  stop_scan / stop_ban_rows   stop tokens, stop sequences and min_tokens (stop=; no counterpart)
+  ban_rows               banned sequences and no-repeat n-grams on the target's logits, per row from the committed text and the
+                         row's ordered path (ban=; no counterpart)
   tree_commit / tree_commit_stochastic   end of a round at temperature 0 / > 0  llama_glide.py:1093-1121
   linear / linear_multi / mlp_gate_up   the projections of a decode pass (M <= 80 token rows):
                          q/k/v/o_proj llama.py:361-363,390, LlamaMLP (qwen2.py:218-230), lm_head llama_glide.py:1091
@@ -637,6 +640,64 @@ def stop_ban_rows(logits: torch.Tensor, table: torch.Tensor, base: Optional[torc
     _C.check(_C.load().ls_stop_ban_rows(x.data_ptr(), b, R, V, _dtype(x), x.stride(0), max(x.stride(1), V), tab_p, STOP_TABLE_WORDS,
                                         _len_i32(base, b, "base"), _len_i32(base_sub, b, "base_sub"), int(base_add), mode,
                                         mask_p or None, mask_sb, mask_sr, mask_c, _stream()), "ls_stop_ban_rows")
+    return logits
+
+
+BAN_TABLE_WORDS = 1093     # int32 words of a ban table (longspec_amd/ban.py, LS_BAN_TABLE_WORDS)
+BAN_CHUNK = 1024           # text columns per workgroup of the no-repeat scan (LS_BAN_CHUNK)
+BAN_MAX_EXTRA = 128        # columns of extra_ids (LS_BAN_MAX_EXTRA): a verification pass has at most 80 rows
+
+
+def ban_rows(logits: torch.Tensor, table: torch.Tensor, output_ids: Optional[torch.Tensor], base: Optional[torch.Tensor] = None,
+             base_sub: Optional[torch.Tensor] = None, base_add: int = 0, extra_ids: Optional[torch.Tensor] = None,
+             extra_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Banned sequences and no-repeat n-grams on TARGET logits [b, V] or [b, R, V] (16-bit, unit column stride, any
+    non-overlapping row strides), IN PLACE (``ls_ban_rows``, one launch; the definition is ``longspec_amd/ban.py``).  The text of
+    row r of batch z is ``output_ids[z, :w]`` (int64 [b, W]; None: no columns), ``w = base[z] - base_sub[z] + base_add`` (int32
+    [b] tensors on the device, None: 0; clamped to 0..W), followed by every ``extra_ids[z, c]`` (int64 [b, C]) with
+    ``extra_mask[z, r, c] != 0`` (int64 [b, R, C], or [R, C] = one mask for the whole batch) in increasing ``c``.  The last
+    token of every sequence of ``table`` (``Ban.table``) whose front ends that text, and every token that would complete an
+    n-gram the text already holds, become -inf; every other element keeps its bits.  The grid is sized from W and C: nothing is
+    read back.  Returns ``logits``."""
+    _dev(logits, table, output_ids, base, base_sub, extra_ids, extra_mask)
+    if logits.dim() not in (2, 3) or logits.dtype not in (torch.float16, torch.bfloat16) or logits.stride(-1) != 1:
+        raise TypeError("ban_rows: logits must be fp16 / bf16 [b, V] or [b, R, V] with unit column stride")
+    x = logits if logits.dim() == 3 else logits.unsqueeze(1)
+    b, R, V = x.shape
+    if (R > 1 and x.stride(1) < V) or (b > 1 and x.stride(0) < V):
+        raise ValueError("ban_rows: overlapping rows")
+    if table.dtype != torch.int32 or table.dim() != 1 or table.numel() != BAN_TABLE_WORDS or not table.is_contiguous():
+        raise TypeError(f"ban_rows: table must be a contiguous int32 [{BAN_TABLE_WORDS}] tensor (Ban.table)")
+    out_p, out_sb, W = None, 0, 0
+    if output_ids is not None:
+        if output_ids.dtype != torch.int64 or output_ids.dim() != 2 or output_ids.shape[0] != b or output_ids.stride(1) != 1:
+            raise TypeError(f"ban_rows: output_ids must be int64 [{b}, W] with contiguous rows")
+        W = output_ids.shape[1]
+        if b > 1 and output_ids.stride(0) < W:
+            raise ValueError("ban_rows: output_ids rows must be at least W elements apart")
+        out_p, out_sb = (output_ids.data_ptr(), max(output_ids.stride(0), W)) if W else (None, 0)
+    C = 0
+    ids_p = mask_p = None
+    ids_sb = mask_sb = mask_sr = 0
+    if extra_ids is not None and extra_ids.shape[-1] > 0:
+        if extra_mask is None:
+            raise ValueError("ban_rows: extra_ids needs extra_mask")
+        C = extra_ids.shape[-1]
+        if C > BAN_MAX_EXTRA:
+            raise ValueError(f"ban_rows: {C} extra columns, at most {BAN_MAX_EXTRA}")
+        if extra_ids.dtype != torch.int64 or extra_ids.dim() != 2 or extra_ids.shape[0] != b or extra_ids.stride(1) != 1:
+            raise TypeError("ban_rows: extra_ids must be int64 [b, C] with contiguous rows")
+        if extra_mask.dtype != torch.int64 or extra_mask.dim() not in (2, 3) or extra_mask.stride(-1) != 1 \
+                or tuple(extra_mask.shape[-2:]) != (R, C) or (extra_mask.dim() == 3 and extra_mask.shape[0] != b):
+            raise TypeError("ban_rows: extra_mask must be int64 [b, R, C] or [R, C] with unit column stride")
+        ids_p, ids_sb = extra_ids.data_ptr(), extra_ids.stride(0)
+        mask_p, mask_sr = extra_mask.data_ptr(), extra_mask.stride(-2)
+        mask_sb = extra_mask.stride(0) if extra_mask.dim() == 3 else 0
+    elif extra_mask is not None and extra_ids is None:
+        raise ValueError("ban_rows: extra_mask needs extra_ids")
+    _C.check(_C.load().ls_ban_rows(x.data_ptr(), b, R, V, _dtype(x), x.stride(0), max(x.stride(1), V), table.data_ptr(),
+                                   BAN_TABLE_WORDS, out_p, out_sb, W, _len_i32(base, b, "base"), _len_i32(base_sub, b, "base_sub"),
+                                   int(base_add), ids_p, ids_sb, mask_p, mask_sb, mask_sr, C, _stream()), "ls_ban_rows")
     return logits
 
 
