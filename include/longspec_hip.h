@@ -479,6 +479,53 @@ int ls_ban_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t str
                 const int32_t* base_sub, int base_add, const int64_t* extra_ids, int64_t ids_stride_b, const int64_t* extra_mask,
                 int64_t mask_stride_b, int64_t mask_stride_r, int n_extra, void* stream);
 
+/* Guided decoding: a deterministic automaton over token ids on the target's logits (guide=; csrc/guide.hip; no counterpart in
+ * the reference).  table: int32 [table_words] on the device, 16-byte aligned (longspec_amd/guide.py builds it) --
+ *   [0] S >= 1   [1] C (1..LS_GUIDE_MAX_CLASSES)   [2] start   [3] vocab   [4] the word count   [5:8] reserved (0)
+ *   [8 : 8 + K]  the classes of ids 0 .. vocab-1 as 16-bit values, two per word, the even id in the low half, LS_GUIDE_NO_CLASS
+ *                (0xFFFF) = forbidden in every state; K = ceil(vocab / 2) rounded up to a multiple of 4 words (padding 0xFFFF),
+ *                so that the transition area starts 16-byte aligned
+ *   [8 + K : 8 + K + S * C]  next, int32 [S, C] row-major: the state behind a token of class c in state s, -1 = no transition
+ * with S * C <= LS_GUIDE_MAX_CELLS.  walk(s, id) = -1 where s < 0, id lies outside [0, vocab) or its class is forbidden (0xFFFF,
+ * or a value >= C), else next[s, class(id)], a value outside [-1, S) counting as -1.  A header whose S, C, vocab are out of range
+ * or whose areas do not fit table_words makes every row dead and every state -1: nothing read from the table indexes memory
+ * unclamped.
+ *
+ * ls_guide_rows: 16-bit logits [b, rows, vocab] (strides in elements, unit column stride, rows must not overlap), IN PLACE, one
+ * launch.  Row r of batch z starts in s = state[z] (int32 [b]; outside [-1, S): -1) and walks every extra_ids[z, c], c <
+ * n_extra, with extra_mask[z, r, c] != 0, IN INCREASING c (extra_ids int64, row stride ids_stride_b; extra_mask int64, strides
+ * mask_stride_b -- 0: one mask for the batch -- and mask_stride_r, unit column stride; n_extra 0..LS_GUIDE_MAX_EXTRA), ids
+ * bounded by the smaller of `vocab` and the table's.  s < 0 behind the walk: the row is DEAD and every element keeps its bits (a
+ * committed state of -1 leaves all its rows alone).  Otherwise every v in [0, vocab) with walk(s, v) < 0 -- ids at or beyond the
+ * table's vocab included -- gets the type's -inf pattern (0xfc00 / 0xff80); every other element keeps its bits, NaN payloads, -0.0
+ * and the gaps between rows included.  The logits are never read.  Grid (ceil(vocab / LS_GUIDE_SLICE), rows, b) workgroups of 256:
+ * every workgroup redoes its row's walk (the path assembled by ballot + prefix, the classes of all path tokens looked up in
+ * parallel, the chain through next serial), packs next[s, :] into C allow bits in LDS and streams its slice of the vocabulary with
+ * 16-byte class loads; a group of eight ids that is wholly forbidden at a 16-byte aligned address is one 16-byte store, a wholly
+ * allowed one nothing, anything else 16-bit stores of the forbidden ids (a row that is only 2-byte aligned, the ragged tail of a
+ * vocab that is no multiple of 8).  The grid depends on host-side shapes only: nothing is read back, safe inside a replayed
+ * graph.  Exact; no workspace, no atomics, no floating point.  LS_ERR_INVALID_ARG, before any launch: null logits / table /
+ * state, a dtype that is not 16-bit, b or rows outside 1..65535, vocab < 1, stride_r < vocab, table_words < LS_GUIDE_HEADER_WORDS,
+ * a table that is not 16-byte aligned, n_extra outside 0..LS_GUIDE_MAX_EXTRA or without its two tensors.
+ *
+ * ls_guide_advance: state[z] (int32 [b], IN PLACE) = state[z] walked along ids[z, j], j < min(num[z * num_stride], n) (ids int64
+ * [b, n], row stride ids_stride_b; num int64, NULL: all n; negative: 0; n 1..LS_GUIDE_MAX_EXTRA), ids bounded by the table's
+ * vocab.  -1 stays -1.  One wave per batch row: the classes in parallel, the chain serial.  One launch, graph-safe; the same
+ * refusals for b, n, the table and negative strides. */
+#define LS_GUIDE_HEADER_WORDS 8
+#define LS_GUIDE_MAX_CLASSES 16384
+#define LS_GUIDE_MAX_CELLS 16777216
+#define LS_GUIDE_NO_CLASS 65535
+#define LS_GUIDE_MAX_EXTRA 128
+#ifndef LS_GUIDE_SLICE       /* (measurement builds set another slice: tools/ab_guide_round.py; a multiple of 2048) */
+#define LS_GUIDE_SLICE 8192
+#endif
+int ls_guide_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t stride_b, int64_t stride_r, const int32_t* table,
+                  int table_words, const int32_t* state, const int64_t* extra_ids, int64_t ids_stride_b, const int64_t* extra_mask,
+                  int64_t mask_stride_b, int64_t mask_stride_r, int n_extra, void* stream);
+int ls_guide_advance(int32_t* state, int b, const int32_t* table, int table_words, const int64_t* ids, int n, int64_t ids_stride_b,
+                     const int64_t* num, int64_t num_stride, void* stream);
+
 /* The drafter of prompt-lookup (n-gram) speculation (lookup_generate; csrc/lookup.hip; no counterpart in the reference, whose
  * every loop needs a trained draft layer).  The text of batch row z is T = prompt_ids[z, :il] ++ output_ids[z, :w], il =
  * input_len[z] clamped to 0..prompt_cols, w = cache_lens[z] - input_len[z] + 1 clamped to 0..out_cap (the columns written so far,

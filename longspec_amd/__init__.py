@@ -11,3 +11,4 @@ from .penalties import Penalties  # noqa: E402,F401
 from .logprobs import Logprobs  # noqa: E402,F401
 from .stop import Stop  # noqa: E402,F401
 from .ban import Ban  # noqa: E402,F401
+from .guide import Guide  # noqa: E402,F401

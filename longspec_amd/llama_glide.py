@@ -27,6 +27,7 @@ from .penalties import resolve as _resolve_penalties
 from .logprobs import new_buffers as _logprob_buffers, resolve as _resolve_logprobs
 from .stop import new_state as _stop_state, resolve as _resolve_stop, result_of as _stop_result
 from .ban import resolve as _resolve_ban
+from .guide import resolve as _resolve_guide
 from .lookup import check as _lookup_check
 from .llama import (DecodeLinear, LlamaForCausalLM, LlamaMLP, LlamaRMSNorm, chunked_causal_prefill,
                     project_qkv, _default_ops)
@@ -437,6 +438,24 @@ class LlamaGlide(LlamaForCausalLM):
             table = ban.table(self.lm_head.out_features, device)
         st.ban = SimpleNamespace(cfg=ban, table=table)
 
+    def _begin_guide(self, st, guide, bsz: int, device, first_token, table=None):
+        """The guide part of a decode state: ``st.guide`` = None, or a namespace of ``cfg`` (the ``Guide``), ``table`` (its int32
+        device table, ``table`` when the caller has built it already, for the first token -- built now, never inside a graph
+        capture) and ``state``, int32 [bsz]: the automaton's state behind the committed text, here ``start`` advanced by
+        ``first_token``; ``ops.guide_advance`` moves it behind every commit.  Like the penalty state it is not rolled back by
+        ``stop=``.  Refused under a vocabulary-parallel shard: no rank holds a whole row of logits there."""
+        st.guide = None
+        if guide is None:
+            return
+        sh = self.model.layers[-1].self_attn.shard
+        if sh is not None and sh.vocab_parallel:
+            raise ValueError("guide= is not available with a vocabulary-parallel shard")
+        if table is None:
+            table = guide.table(self.lm_head.out_features, device)
+        state = torch.full((bsz,), guide.start, dtype=torch.int32, device=device)
+        self.ops.guide_advance(state, table, first_token.to(device=device, dtype=torch.int64).view(bsz, 1))
+        st.guide = SimpleNamespace(cfg=guide, table=table, state=state)
+
     def _stop_scan(self, st, written, written_sub=None, written_add=0, num=None, fill=0, state=None):
         """``ops.stop_scan`` on a decode state: the columns this round (``num`` per row; None: one) wrote to ``st.output_ids``,
         erasing ``st.spec_mask`` and ``st.logprobs`` along with it where the state has them."""
@@ -444,11 +463,12 @@ class LlamaGlide(LlamaForCausalLM):
                            num=num, fill=fill, state=state, spec_mask=getattr(st, "spec_mask", None), logprobs=st.logprobs)
 
     def _first_token(self, logits, sampling, input_len, penalties=None, prompt_state=None, logprobs=None, stop=None,
-                     stop_table=None, ban_table=None):
+                     stop_table=None, ban_table=None, guide=None, guide_table=None):
         """The prefill's token from ``logits`` [bsz, V] of prompt row ``input_len - 1``; under ``penalties`` the history of
         that row is the prompt alone (``prompt_state``: ``_token_state`` of the prompt); under a ``stop`` with ``min_tokens > 0``
         the stop ids of ``stop_table`` are banned from it (column 0); under ``ban_table`` (``Ban.table``) the one-token sequences
-        are (its text is empty).  Returns (token, its log-prob rows
+        are (its text is empty); under ``guide`` with ``guide_table`` (``Guide.table``) the tokens without a transition from
+        ``guide.start`` are.  Returns (token, its log-prob rows
         (``ops.token_logprobs``) under ``logprobs``, else None)."""
         if penalties is not None:
             logits = self.ops.penalize_rows(logits, prompt_state, penalties)
@@ -456,6 +476,9 @@ class LlamaGlide(LlamaForCausalLM):
             logits = self.ops.stop_ban_rows(logits, stop_table)
         if ban_table is not None:
             logits = self.ops.ban_rows(logits, ban_table, None)
+        if guide is not None:
+            start = torch.full((logits.size(0),), guide.start, dtype=torch.int32, device=logits.device)
+            logits = self.ops.guide_rows(logits, guide_table, start)
         if sampling is None:
             token = logits.argmax(dim=-1)
         else:
@@ -488,7 +511,7 @@ class LlamaGlide(LlamaForCausalLM):
 
     @torch.inference_mode()
     def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645, sampling=None,
-                         penalties=None, logprobs=None, stop=None, ban=None):                                      # :552-585
+                         penalties=None, logprobs=None, stop=None, ban=None, guide=None):                                      # :552-585
         """``sampling`` (``longspec_amd.Sampling``): every token is drawn from the target's filtered distribution instead of
         taken as its arg-max -- the denominator of a sampled speculative run, and with the same seed the same text.
         ``penalties`` (``longspec_amd.Penalties``): the logits of every step are penalised from the prompt and the text so far.
@@ -501,7 +524,9 @@ class LlamaGlide(LlamaForCausalLM):
         EOS test runs alongside, unchanged.  ``num``, the KV lengths and the penalty state are not rolled back: they describe
         the steps that ran, ``last_stop.length`` is the authority on the text.
         ``ban`` (``longspec_amd.Ban``): banned sequences and no-repeat n-grams (``ban.py``): the tokens the text so far forbids
-        are -inf in every step's logits, behind the penalties and in front of the arg-max or draw and the log-probs."""
+        are -inf in every step's logits, behind the penalties and in front of the arg-max or draw and the log-probs.
+        ``guide`` (``longspec_amd.Guide``): guided decoding (``guide.py``): the tokens without a transition from the state behind
+        the text so far are -inf in every step's logits, at the same place; the state advances behind every token."""
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, None, use_env=True)
         pen = _resolve_penalties(penalties, None, use_env=True)
@@ -510,6 +535,8 @@ class LlamaGlide(LlamaForCausalLM):
         stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
         bn = _resolve_ban(ban, None, use_env=True)
         btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
+        gd = _resolve_guide(guide, None, use_env=True)
+        gtab = gd.table(self.lm_head.out_features, input_ids.device) if gd is not None else None
         self._clear_shard()
         bsz = input_ids.size(0)
         output_ids = input_ids.new_zeros((bsz, max_gen_len))
@@ -522,7 +549,7 @@ class LlamaGlide(LlamaForCausalLM):
         rows = torch.arange(bsz, device=input_ids.device)
         pstate = self._token_state(bsz, input_ids.device, input_ids, input_len) if pen is not None else None
         output_ids[:, 0], first_lp = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), sampling, input_len,
-                                                       pen, pstate, lpc, stp, stab, btab)
+                                                       pen, pstate, lpc, stp, stab, btab, gd, gtab)
         cache_lens += input_len.int()
         num = 0
         eos = self._stop_id(eos_id, "vanilla")
@@ -535,7 +562,7 @@ class LlamaGlide(LlamaForCausalLM):
             ev0.record()
         vs = self.begin_vanilla_decode(output_ids, cache_lens, input_len.int(), P, sampling=sampling, penalties=penalties,
                                        prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp,
-                                       stop=stop, stop_table=stab, ban=ban, ban_table=btab)
+                                       stop=stop, stop_table=stab, ban=ban, ban_table=btab, guide=guide, guide_table=gtab)
         self.last_logprobs = vs.logprobs
         self.last_stop = vs.last_stop
         for step in range(1, max_gen_len):
@@ -578,7 +605,7 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int, sampling=None, penalties=None,
                              prompt_ids=None, prompt_state=None, logprobs=None, first_logprobs=None, stop=None, stop_table=None,
-                             ban=None, ban_table=None):
+                             ban=None, ban_table=None, guide=None, guide_table=None):
         """State of the vanilla loop (``llama_glide.py:566-583``): ``output_ids`` [bsz, max_gen] with the first
         token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32.  ``sampling``:
         draw instead of arg-max (None: the process-wide default LONGSPEC_SAMPLING, else greedy).  ``penalties``: penalise
@@ -590,19 +617,24 @@ class LlamaGlide(LlamaForCausalLM):
         ``stop_table``: its device table, already built) and keeps ``vs.stop_state`` / ``vs.last_stop``; column 0 is tested
         here.  A row that has stopped keeps decoding with the batch, and every step erases what it wrote; KV lengths and the
         penalty state are not rolled back.  ``ban``: every step's logits carry -inf where the text so far forbids a token
-        (``ban.py``; None: the process-wide default LONGSPEC_BAN, else none; ``ban_table``: its device table, already built)."""
+        (``ban.py``; None: the process-wide default LONGSPEC_BAN, else none; ``ban_table``: its device table, already built).
+        ``guide``: every step's logits carry -inf where the automaton has no transition from ``vs.guide.state``, which starts
+        from the first token and advances behind every step (``guide.py``; None: the process-wide default LONGSPEC_GUIDE, else
+        none; ``guide_table``: its device table, already built)."""
         dev = output_ids.device
         sampling = _resolve_sampling(sampling, None, use_env=True)
         penalties = _resolve_penalties(penalties, None, use_env=True)
         logprobs = _resolve_logprobs(logprobs, None, use_env=True)
         stop = _resolve_stop(stop, None, use_env=True)
         ban = _resolve_ban(ban, None, use_env=True)
+        guide = _resolve_guide(guide, None, use_env=True)
         vs = _DecodeState(output_ids=output_ids, cache_lens=cache_lens, input_len=input_len, P=prompt_bound, step=0,
                           rows=torch.arange(output_ids.size(0), device=dev), sampling=sampling, penalties=penalties)
         self._begin_penalties(vs, penalties, output_ids.size(0), dev, prompt_ids, input_len, output_ids[:, 0], prompt_state)
         self._begin_logprobs(vs, logprobs, output_ids.size(0), output_ids.size(1), dev, first_logprobs)
         self._begin_stop(vs, stop, output_ids.size(0), dev, stop_table)
         self._begin_ban(vs, ban, dev, ban_table)
+        self._begin_guide(vs, guide, output_ids.size(0), dev, output_ids[:, 0], guide_table)
         if vs.stop is not None:
             self._stop_scan(vs, cache_lens, input_len, 1)
         vs.streams = torch.arange(output_ids.size(0), device=dev, dtype=torch.int32) if sampling is not None else None
@@ -624,6 +656,8 @@ class LlamaGlide(LlamaForCausalLM):
             logits = self.ops.stop_ban_rows(logits, vs.stop.table, base=cl, base_sub=il, base_add=1)
         if vs.ban is not None:                                # the text so far: columns 0 .. cl - il
             logits = self.ops.ban_rows(logits, vs.ban.table, out, base=cl, base_sub=il, base_add=1)
+        if vs.guide is not None:                              # the state behind columns 0 .. cl - il
+            logits = self.ops.guide_rows(logits, vs.guide.table, vs.guide.state)
         llm_output = self._target_tokens(logits, vs.sampling, cl, vs.streams)
         cl += 1
         out[rows, (cl - il).long()] = llm_output.view(-1)
@@ -633,6 +667,8 @@ class LlamaGlide(LlamaForCausalLM):
                                     (cl - il).to(torch.int32))
         if vs.penalties is not None:
             self.ops.token_state_add(vs.token_state, llm_output.view(out.size(0), 1))
+        if vs.guide is not None:
+            self.ops.guide_advance(vs.guide.state, vs.guide.table, llm_output.view(out.size(0), 1))
         if vs.stop is not None:
             self._stop_scan(vs, cl, il, 1)
 
@@ -660,18 +696,18 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def spec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                      sampling=None, penalties=None, logprobs=None, stop=None, ban=None):                          # :621-774
+                      sampling=None, penalties=None, logprobs=None, stop=None, ban=None, guide=None):                          # :621-774
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="glide",
-                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop, ban=ban)
+                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide)
 
     @torch.inference_mode()
     def magicdec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                          sampling=None, penalties=None, logprobs=None, stop=None, ban=None):                      # :776-913
+                          sampling=None, penalties=None, logprobs=None, stop=None, ban=None, guide=None):                      # :776-913
         """The MagicDec baseline of the reference's harness (``--method magicdec``): chain speculation where the
         drafter is the TARGET itself attending to a StreamingLLM cache (32 sink rows + the last 1024 prompt rows +
         what it generates), verified exactly like ``spec_generate``.  Same return tuple."""
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="magicdec",
-                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop, ban=ban)
+                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide)
 
     @torch.inference_mode()
     def vanilla_torch_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645):                      # :587-619
@@ -682,7 +718,7 @@ class LlamaGlide(LlamaForCausalLM):
         return self.vanilla_generate(input_ids, prompt_length, max_gen_len=max_gen_len, eos_id=eos_id)
 
     def _chain_generate(self, input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter, sampling=None,
-                        penalties=None, logprobs=None, stop=None, ban=None):
+                        penalties=None, logprobs=None, stop=None, ban=None, guide=None):
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         pen = _resolve_penalties(penalties, temperature, use_env=True)
@@ -691,7 +727,9 @@ class LlamaGlide(LlamaForCausalLM):
         stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
         bn = _resolve_ban(ban, temperature, use_env=True)
         btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
-        magic = drafter == "magicdec"       # (temperature > 0: the same rejection block in both loops, :715-736 = :854-875)
+        gd = _resolve_guide(guide, temperature, use_env=True)
+        gtab = gd.table(self.lm_head.out_features, input_ids.device) if gd is not None else None
+        magic = drafter == "magicdec"      # (temperature > 0: the same rejection block in both loops, :715-736 = :854-875)
         self._clear_shard()
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
@@ -713,11 +751,11 @@ class LlamaGlide(LlamaForCausalLM):
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=cache_lens.clone(), llm_kv_len=cache_lens.clone(), exec_type="prefill")
         pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
-        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab, btab)
+        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab, btab, gd, gtab)
         st = self.begin_chain_decode(first, cache_lens, input_len, P, gamma, max_gen_len, eos_id, temperature, drafter,
                                      first_logits=logits, sampling=sampling, penalties=penalties, prompt_ids=input_ids,
                                      prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp, stop=stop, stop_table=stab,
-                                     ban=ban, ban_table=btab)
+                                     ban=ban, ban_table=btab, guide=guide, guide_table=gtab)
         self.last_logprobs = st.logprobs
         self.last_stop = st.last_stop
         _sync(input_ids)
@@ -732,7 +770,7 @@ class LlamaGlide(LlamaForCausalLM):
     def begin_chain_decode(self, first_token, cache_lens, input_len, prompt_bound: int, gamma=4, max_gen_len=64, eos_id=151645,
                            temperature=0.0, drafter="glide", first_logits=None, sampling=None, penalties=None, prompt_ids=None,
                            prompt_state=None, logprobs=None, first_logprobs=None, stop=None, stop_table=None, ban=None,
-                           ban_table=None):
+                           ban_table=None, guide=None, guide_table=None):
         """State of the chain-speculation loop right after the prefills (``llama_glide.py:641-668``): ``first_token`` [bsz]
         = the target's first generated token, ``cache_lens`` [bsz] int32 = valid rows of every cache (the draft's included),
         ``input_len`` [bsz] = prompt length, ``prompt_bound`` = host-side bound of it.  Also the entry point of benchmarks
@@ -749,7 +787,11 @@ class LlamaGlide(LlamaForCausalLM):
         host counters ``count`` / ``num`` / ``emitted`` are not rolled back: a stopped state is final.  ``ban``: verification row
         i carries -inf where the text so far plus the i draft tokens it follows forbid a token (``ban.py``; None at temperature
         0: the process-wide default LONGSPEC_BAN, else none; ``ban_table``: its device table, already built); the drafter stays
-        unbanned."""
+        unbanned.  ``guide``: verification row i carries -inf where the automaton has no transition from ``st.guide.state`` (the
+        state behind the text so far, advanced behind every commit) walked along the i draft tokens it follows; a row whose
+        draft tokens leave the language keeps its bits and is never accepted (``guide.py``; None at temperature 0: the
+        process-wide default LONGSPEC_GUIDE, else none; ``guide_table``: its device table, already built); the drafter stays
+        unguided."""
         bsz = first_token.size(0)
         dev = first_token.device
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
@@ -757,6 +799,7 @@ class LlamaGlide(LlamaForCausalLM):
         logprobs = _resolve_logprobs(logprobs, temperature, use_env=True)
         stop = _resolve_stop(stop, temperature, use_env=True)
         ban = _resolve_ban(ban, temperature, use_env=True)
+        guide = _resolve_guide(guide, temperature, use_env=True)
         if drafter != "magicdec":
             self._head_of_draft_passes()                # the draft passes' head and its pack exist before the first round
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
@@ -764,8 +807,9 @@ class LlamaGlide(LlamaForCausalLM):
         st.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if sampling is not None else None
         self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
         self._begin_ban(st, ban, dev, ban_table)
+        self._begin_guide(st, guide, bsz, dev, first_token, guide_table)
         st.chain_mask = None
-        if penalties is not None or st.ban is not None:
+        if penalties is not None or st.ban is not None or st.guide is not None:
             # verification row i follows the draft tokens spec_buffer[:, 1 : i + 1]
             st.chain_mask = torch.ones((gamma + 1, gamma), dtype=torch.int64, device=dev).tril(-1)
         self._begin_logprobs(st, logprobs, bsz, max_gen_len + gamma, dev, first_logprobs)
@@ -857,6 +901,9 @@ class LlamaGlide(LlamaForCausalLM):
             llm_verify_logits = self.ops.ban_rows(llm_verify_logits, st.ban.table, output_ids, base=cache_lens,
                                                   base_sub=st.input_len_i32, base_add=1, extra_ids=spec_buffer[:, 1:],
                                                   extra_mask=st.chain_mask)
+        if st.guide is not None:                             # row i: the committed state walked along i draft tokens
+            llm_verify_logits = self.ops.guide_rows(llm_verify_logits, st.guide.table, st.guide.state,
+                                                    extra_ids=spec_buffer[:, 1:], extra_mask=st.chain_mask)
         # (sampling: verification row i was rotated to position cache_lens + i, models' forward :571-577)
         llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
                                                 cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
@@ -876,6 +923,8 @@ class LlamaGlide(LlamaForCausalLM):
                                       next_spec_start_token, st.eos, **({"accept_mask": accept} if accept is not None else {}))
         if st.penalties is not None:                         # the correct_len tokens this round wrote, before the host read
             self.ops.token_state_add(st.token_state, llm_verify_output, num=state[:, 0])
+        if st.guide is not None:                             # ... and the automaton follows them
+            self.ops.guide_advance(st.guide.state, st.guide.table, llm_verify_output, num=state[:, 0])
         if lp_rows is not None:                              # ... and their log-probs, to the columns chain_commit wrote
             self.ops.logprob_commit(lp_rows, st.logprobs, lp_base, base_add=1, num=state[:, 0])
         if st.stop is not None:                              # the stop test on those columns; a hit rides in state[:, 1] (bit 1)
@@ -894,7 +943,7 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def lookup_generate(self, input_ids, prompt_length, gamma=7, max_ngram=3, min_ngram=1, max_gen_len=64, eos_id=151645,
-                        sampling=None, penalties=None, logprobs=None, stop=None, branches=1, ban=None):
+                        sampling=None, penalties=None, logprobs=None, stop=None, branches=1, ban=None, guide=None):
         """Prompt-lookup (n-gram) speculation (no counterpart in the reference): chain speculation whose drafter is the text
         itself -- the ``gamma`` tokens that followed the most recent earlier occurrence of the last ``min_ngram .. max_ngram``
         tokens of prompt + output (``lookup.py``) -- verified exactly like ``spec_generate``.  No draft weights, no draft KV,
@@ -921,11 +970,13 @@ class LlamaGlide(LlamaForCausalLM):
         stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
         bn = _resolve_ban(ban, None, use_env=True)
         btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
+        gd = _resolve_guide(guide, None, use_env=True)
+        gtab = gd.table(self.lm_head.out_features, input_ids.device) if gd is not None else None
         self._clear_shard()
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
         dev = input_ids.device
-        self.set_max_gen_len(max_gen_len + (128 if branches == 1 else 256))      # (a tree pass appends up to 80 rows)
+        self.set_max_gen_len(max_gen_len + (128 if branches == 1 else 256))     # (a tree pass appends up to 80 rows)
         P = int(input_ids.size(1))
         self._set_hints(P, P)
         hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
@@ -934,11 +985,11 @@ class LlamaGlide(LlamaForCausalLM):
         logits = self.lm_head(hidden_states[rows, input_len - 1, :])
         cache_lens = input_ids.new_zeros((bsz)).int() + input_len.int()
         pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
-        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab, btab)
+        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab, btab, gd, gtab)
         st = self.begin_lookup_decode(first, cache_lens, input_len, P, input_ids, gamma, max_ngram, min_ngram, max_gen_len, eos_id,
                                       sampling=sampling, penalties=penalties, prompt_state=pstate, logprobs=logprobs,
                                       first_logprobs=first_lp, stop=stop, stop_table=stab, branches=branches, ban=ban,
-                                      ban_table=btab)
+                                      ban_table=btab, guide=guide, guide_table=gtab)
         self.last_logprobs = st.logprobs
         self.last_stop = st.last_stop
         self.last_lookup = st.last_lookup
@@ -954,7 +1005,7 @@ class LlamaGlide(LlamaForCausalLM):
     def begin_lookup_decode(self, first_token, cache_lens, input_len, prompt_bound: int, prompt_ids, gamma=7, max_ngram=3,
                             min_ngram=1, max_gen_len=64, eos_id=151645, sampling=None, penalties=None, prompt_state=None,
                             logprobs=None, first_logprobs=None, stop=None, stop_table=None, branches=1, ban=None,
-                            ban_table=None):
+                            ban_table=None, guide=None, guide_table=None):
         """State of the prompt-lookup loop right after the target's prefill: the arguments of ``begin_chain_decode`` that have
         a meaning without a drafter, plus ``prompt_ids`` [bsz, P] -- here not optional: ``prompt_ids[z, :input_len[z]]`` is the
         front of the text the drafter searches (and, under ``penalties``, the source of the prompt flags).  Also the entry point
@@ -969,10 +1020,11 @@ class LlamaGlide(LlamaForCausalLM):
         logprobs = _resolve_logprobs(logprobs, None, use_env=True)
         stop = _resolve_stop(stop, None, use_env=True)
         ban = _resolve_ban(ban, None, use_env=True)
+        guide = _resolve_guide(guide, None, use_env=True)
         if branches > 1:
             return self._begin_lookup_tree(first_token, cache_lens, input_len, int(prompt_bound), prompt_ids, gamma, branches,
                                            max_ngram, min_ngram, max_gen_len, eos_id, sampling, penalties, prompt_state, logprobs,
-                                           first_logprobs, stop, stop_table, ban, ban_table)
+                                           first_logprobs, stop, stop_table, ban, ban_table, guide, guide_table)
         st = _DecodeState(gamma=gamma, max_ngram=max_ngram, min_ngram=min_ngram, bsz=bsz, P=int(prompt_bound),
                           max_gen_len=max_gen_len, count=0, num=0, emitted=1, rounds=0, sampling=sampling)
         st.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if sampling is not None else None
@@ -981,8 +1033,9 @@ class LlamaGlide(LlamaForCausalLM):
             st.prompt_ids = st.prompt_ids.contiguous()
         self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
         self._begin_ban(st, ban, dev, ban_table)
+        self._begin_guide(st, guide, bsz, dev, first_token, guide_table)
         st.chain_mask = None
-        if penalties is not None or st.ban is not None:
+        if penalties is not None or st.ban is not None or st.guide is not None:
             # verification row i follows the draft tokens spec_buffer[:, 1 : i + 1]
             st.chain_mask = torch.ones((gamma + 1, gamma), dtype=torch.int64, device=dev).tril(-1)
         self._begin_logprobs(st, logprobs, bsz, max_gen_len + gamma, dev, first_logprobs)
@@ -1031,6 +1084,9 @@ class LlamaGlide(LlamaForCausalLM):
             llm_verify_logits = self.ops.ban_rows(llm_verify_logits, st.ban.table, output_ids, base=cache_lens,
                                                   base_sub=st.input_len_i32, base_add=1, extra_ids=spec_buffer[:, 1:],
                                                   extra_mask=st.chain_mask)
+        if st.guide is not None:                             # row i: the committed state walked along i draft tokens
+            llm_verify_logits = self.ops.guide_rows(llm_verify_logits, st.guide.table, st.guide.state,
+                                                    extra_ids=spec_buffer[:, 1:], extra_mask=st.chain_mask)
         # (sampling: verification row i was rotated to position cache_lens + i)
         llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
                                                 cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
@@ -1044,6 +1100,8 @@ class LlamaGlide(LlamaForCausalLM):
                                       st.next_spec_start_token, st.eos)
         if st.penalties is not None:                         # the correct_len tokens this round wrote, before the host read
             self.ops.token_state_add(st.token_state, llm_verify_output, num=state[:, 0])
+        if st.guide is not None:                             # ... and the automaton follows them
+            self.ops.guide_advance(st.guide.state, st.guide.table, llm_verify_output, num=state[:, 0])
         if lp_rows is not None:                              # ... and their log-probs, to the columns chain_commit wrote
             self.ops.logprob_commit(lp_rows, st.logprobs, lp_base, base_add=1, num=state[:, 0])
         if st.stop is not None:                              # the stop test on those columns; a hit rides in state[:, 1] (bit 1)
@@ -1092,7 +1150,7 @@ class LlamaGlide(LlamaForCausalLM):
 
     def _begin_lookup_tree(self, first_token, cache_lens, input_len, P: int, prompt_ids, gamma, branches, max_ngram, min_ngram,
                            max_gen_len, eos_id, sampling, penalties, prompt_state, logprobs, first_logprobs, stop, stop_table,
-                           ban=None, ban_table=None):
+                           ban=None, ban_table=None, guide=None, guide_table=None):
         """State of the lookup loop with ``branches >= 2``: ``begin_tree_decode``'s without anything that belongs to a draft
         layer -- ``all_spec`` / ``tree_mask`` of the static level-major tree (Fn = 1 + branches * gamma nodes), ``acc_pad``
         [bsz, gamma + 1], ``a``, ``emitted_dev``, int32 ``cache_lens``, R = Fn - 1 + gamma + 1 verification rows -- and the
@@ -1114,6 +1172,7 @@ class LlamaGlide(LlamaForCausalLM):
         self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
         self._begin_logprobs(st, logprobs, bsz, width, dev, first_logprobs)
         self._begin_ban(st, ban, dev, ban_table)
+        self._begin_guide(st, guide, bsz, dev, first_token, guide_table)
         st.fill = self._tree_output_fill(eos_id)
         st.output_ids = torch.full((bsz, width), st.fill, dtype=torch.int64, device=dev)
         st.spec_mask = torch.zeros((bsz, width), dtype=torch.int64, device=dev)
@@ -1168,6 +1227,9 @@ class LlamaGlide(LlamaForCausalLM):
         if st.ban is not None:            # row j: the committed columns, then the nodes on its path (level-major: path order)
             llm_logits = ops.ban_rows(llm_logits, st.ban.table, st.output_ids, base=st.emitted_dev, extra_ids=all_spec[:, 1:],
                                       extra_mask=tree_mask[:, :, 1:])
+        if st.guide is not None:          # row j: the committed state walked along the nodes on its path
+            llm_logits = ops.guide_rows(llm_logits, st.guide.table, st.guide.state, extra_ids=all_spec[:, 1:],
+                                        extra_mask=tree_mask[:, :, 1:])
         all_llm_pred = self._target_tokens(llm_logits, st.sampling,
                                            position_ids[:, a - 1:a + Fn - 1] if st.sampling is not None else None)
         # ---- A: the deepest branch that verifies; no KV row moves (the next pass feeds the accepted tokens again)
@@ -1181,6 +1243,8 @@ class LlamaGlide(LlamaForCausalLM):
                                 target_lens=st.cache_lens, target_add=a, emitted_dev=st.emitted_dev)
         if st.penalties is not None:
             ops.token_state_add(st.token_state, acc_pad, num=acc_num_t)
+        if st.guide is not None:
+            ops.guide_advance(st.guide.state, st.guide.table, acc_pad, num=acc_num_t)
         if st.stop is not None:
             self._stop_scan(st, st.emitted_dev, num=acc_num_t, fill=st.fill, state=state)
         # the branch of the deepest accepted node (node = 1 + (d-1) * B + j), where a draft token was accepted at all
@@ -1217,7 +1281,7 @@ class LlamaGlide(LlamaForCausalLM):
     @torch.inference_mode()
     def tree_spec_generate(self, input_ids, prompt_length, tree_shape: Optional[List[int]] = None, max_gen_len=64,
                            eos_id=151645, temperature=0.0, shard=None, sampling=None, penalties=None,
-                           logprobs=None, stop=None, ban=None):                                               # :915-1126
+                           logprobs=None, stop=None, ban=None, guide=None):                                               # :915-1126
         """``shard`` (``dist.KVShard``, every rank of the group calls with the same arguments): the prompt is prefilled
         and its KV kept sequence-sharded over the ranks (``_sharded_prefill``); decoding then runs replicated with one
         exchange per attention call.  Returns the same values on every rank.  ``sampling``: the verification pass draws
@@ -1229,7 +1293,9 @@ class LlamaGlide(LlamaForCausalLM):
         (``stop.py``), the result as ``self.last_stop``; the stop test reads ``output_ids`` only, so every rank of either shard
         computes the same result -- ``min_tokens > 0`` alone is refused with a vocabulary-parallel shard.  ``ban``: banned
         sequences and no-repeat n-grams on every verification row, from the committed text and the row's tree path (``ban.py``;
-        not with a vocabulary-parallel shard; under a sequence shard every rank computes the same rows)."""
+        not with a vocabulary-parallel shard; under a sequence shard every rank computes the same rows).  ``guide``: guided
+        decoding on every verification row, from the state behind the committed text walked along the row's tree path
+        (``guide.py``; not with a vocabulary-parallel shard; under a sequence shard every rank keeps the same state)."""
         assert input_ids is not None, "please give the input"
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         pen = _resolve_penalties(penalties, temperature, use_env=True)
@@ -1248,6 +1314,10 @@ class LlamaGlide(LlamaForCausalLM):
         if bn is not None and shard is not None and shard.vocab_parallel:
             raise ValueError("ban= is not available with a vocabulary-parallel shard")
         btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
+        gd = _resolve_guide(guide, temperature, use_env=True)
+        if gd is not None and shard is not None and shard.vocab_parallel:
+            raise ValueError("guide= is not available with a vocabulary-parallel shard")
+        gtab = gd.table(self.lm_head.out_features, input_ids.device) if gd is not None else None
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
         dev = input_ids.device
@@ -1268,13 +1338,13 @@ class LlamaGlide(LlamaForCausalLM):
                 heads = max(self.config.num_attention_heads, self.glide.config.num_attention_heads)
                 shard.enable_peer_exchange(bsz * 128 * heads * 129, dev)
             first, first_lp = self._sharded_prefill(input_ids, input_len, position_ids, shard, sampling, pen, pstate, lpc, stp,
-                                                    stab, btab)
+                                                    stab, btab, gd, gtab)
         else:
             # prefill LLM (:954-960)
             self._set_hints(P, P)
             hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
             first, first_lp = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), sampling, input_len, pen,
-                                                pstate, lpc, stp, stab, btab)
+                                                pstate, lpc, stp, stab, btab, gd, gtab)
             # prefill glide (:968-975)
             hidden_states = self.model.embed_tokens(input_ids)
             position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
@@ -1282,7 +1352,8 @@ class LlamaGlide(LlamaForCausalLM):
                        cache_lens=lens.clone(), llm_kv_len=lens.clone(), exec_type="prefill")
         st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature, sampling=sampling,
                                     penalties=penalties, prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs,
-                                    first_logprobs=first_lp, stop=stop, stop_table=stab, ban=ban, ban_table=btab)
+                                    first_logprobs=first_lp, stop=stop, stop_table=stab, ban=ban, ban_table=btab, guide=guide,
+                                    guide_table=gtab)
         self.last_logprobs = st.logprobs
         self.last_stop = st.last_stop
         _sync(input_ids)
@@ -1302,7 +1373,7 @@ class LlamaGlide(LlamaForCausalLM):
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
     def _sharded_prefill(self, input_ids, input_len, position_ids, shard, sampling=None, penalties=None, prompt_state=None,
-                         logprobs=None, stop=None, stop_table=None, ban_table=None):
+                         logprobs=None, stop=None, stop_table=None, ban_table=None, guide=None, guide_table=None):
         """Sequence-sharded prefill: rank r runs the target model on prompt rows [r*Ls, (r+1)*Ls) only
         (one all-gather of the layer's K/V rows per layer, ``LlamaAttention.sharded_prefill``) and keeps that slice of the
         KV; the tail rank computes the first token (and, under ``logprobs``, its log-prob rows) and broadcasts it.  The
@@ -1333,7 +1404,7 @@ class LlamaGlide(LlamaForCausalLM):
                         torch.zeros((bsz, 1, logprobs.top_n), dtype=torch.int64, device=dev))
         if shard.is_tail:
             first, first_lp = self._first_token(self.lm_head(hidden_states[:, hi - lo - 1, :]), sampling, input_len, penalties,
-                                                prompt_state, logprobs, stop, stop_table, ban_table)
+                                                prompt_state, logprobs, stop, stop_table, ban_table, guide, guide_table)
         shard.broadcast_from_tail(first)
         for t in first_lp or ():
             if t.numel():
@@ -1344,7 +1415,7 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_tree_decode(self, first_token, cache_lens, prompt_bound: int, tree_shape=None, max_gen_len=64, eos_id=151645,
                           temperature=0.0, sampling=None, penalties=None, prompt_ids=None, prompt_state=None, logprobs=None,
-                          first_logprobs=None, stop=None, stop_table=None, ban=None, ban_table=None):
+                          first_logprobs=None, stop=None, stop_table=None, ban=None, ban_table=None, guide=None, guide_table=None):
         """State of the round loop right after the two prefills (``llama_glide.py:927-991``).
         ``first_token`` [bsz] = the target's first generated token, ``cache_lens`` [bsz] int32 = valid
         rows of every KV cache, ``prompt_bound`` = host-side bound of it.  Also the entry point of
@@ -1363,13 +1434,18 @@ class LlamaGlide(LlamaForCausalLM):
         ``num`` / ``emitted`` are not rolled back: a stopped state is final and ``last_stop.length`` is the authority.  ``ban``:
         verification row j carries -inf where the committed text plus the nodes on node j's path forbid a token (``ban.py``;
         None at temperature 0: the process-wide default LONGSPEC_BAN, else none; ``ban_table``: its device table, already
-        built), inside the round and its graph; the draft passes stay unbanned."""
+        built), inside the round and its graph; the draft passes stay unbanned.  ``guide``: verification row j carries -inf where
+        the automaton has no transition from ``st.guide.state`` (the state behind the committed text, advanced behind every
+        commit inside the round and its graph) walked along the nodes on node j's path; a row whose path leaves the language
+        keeps its bits and is never accepted (``guide.py``; None at temperature 0: the process-wide default LONGSPEC_GUIDE, else
+        none; ``guide_table``: its device table, already built); the draft passes stay unguided."""
         dev = first_token.device
         sampling = _resolve_sampling(sampling, temperature, use_env=True)
         penalties = _resolve_penalties(penalties, temperature, use_env=True)
         logprobs = _resolve_logprobs(logprobs, temperature, use_env=True)
         stop = _resolve_stop(stop, temperature, use_env=True)
         ban = _resolve_ban(ban, temperature, use_env=True)
+        guide = _resolve_guide(guide, temperature, use_env=True)
         sh = self.model.layers[-1].self_attn.shard
         if sampling is not None and sh is not None and sh.vocab_parallel:
             raise ValueError("sampling= is not available with a vocabulary-parallel shard")
@@ -1386,6 +1462,7 @@ class LlamaGlide(LlamaForCausalLM):
         self._begin_penalties(st, penalties, bsz, dev, prompt_ids, cache_lens, first_token, prompt_state)
         self._begin_logprobs(st, logprobs, bsz, max_gen_len, dev, first_logprobs)
         self._begin_ban(st, ban, dev, ban_table)
+        self._begin_guide(st, guide, bsz, dev, first_token, guide_table)
         st.output_ids = torch.full((bsz, max_gen_len), self._tree_output_fill(eos_id), dtype=torch.int64, device=dev)  # :937 (G8)
         st.spec_mask = torch.zeros((bsz, max_gen_len), dtype=torch.int64, device=dev)
         st.output_ids[:, 0] = first_token
@@ -1508,6 +1585,8 @@ class LlamaGlide(LlamaForCausalLM):
                  "acc_pad", "output_ids", "emitted_dev") + (("token_state",) if st.token_state is not None else ()) \
             + (("stop_state",) if st.stop_state is not None else ())
         lp_bufs = (st.logprobs.token, st.logprobs.top_ids, st.logprobs.top) if st.logprobs is not None else ()
+        if st.guide is not None:            # the automaton's state is decode state too: a warm-up round advances it
+            lp_bufs += (st.guide.state,)
         with rp.guard():
             rp.roll_over(st.emitted)
             for a in range(1, st.gamma + 2):
@@ -1614,6 +1693,10 @@ class LlamaGlide(LlamaForCausalLM):
                 # increasing column is increasing depth
                 llm_logits = ops.ban_rows(llm_logits, st.ban.table, st.output_ids, base=st.emitted_dev, extra_ids=all_spec[:, 1:],
                                           extra_mask=tree_mask[:, :, 1:])
+            if st.guide is not None:
+                # row j: the state behind the emitted columns walked along the nodes on its path, in the same order
+                llm_logits = ops.guide_rows(llm_logits, st.guide.table, st.guide.state, extra_ids=all_spec[:, 1:],
+                                            extra_mask=tree_mask[:, :, 1:])
             all_llm_pred = self._target_tokens(llm_logits, st.sampling,
                                                position_ids[:, a - 1:a + Fn - 1] if st.sampling is not None else None)
         # ---- A: accept / reject tree collapse + last-layer KV row move (:1104-1116); the accepted rows start at
@@ -1641,6 +1724,8 @@ class LlamaGlide(LlamaForCausalLM):
                                 emitted_dev=st.emitted_dev)
         if st.penalties is not None:                          # the accepted tokens, inside the round (and its graph)
             ops.token_state_add(st.token_state, acc_pad, num=acc_num_t)
+        if st.guide is not None:                              # ... and the automaton follows them
+            ops.guide_advance(st.guide.state, st.guide.table, acc_pad, num=acc_num_t)
         if st.stop is not None:                               # the stop test on the columns tree_commit wrote; a hit rides in
             self._stop_scan(st, st.emitted_dev, num=acc_num_t, fill=st.fill, state=state)      # state[:, 1] (bit 1)
         return state

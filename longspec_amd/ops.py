@@ -23,6 +23,8 @@ One function per reference seam of the draft-then-verify round:
   stop_scan / stop_ban_rows   stop tokens, stop sequences and min_tokens (stop=; no counterpart)
   ban_rows               banned sequences and no-repeat n-grams on the target's logits, per row from the committed text and the
                          row's ordered path (ban=; no counterpart)
+  guide_rows / guide_advance   guided decoding: the tokens a DFA over token ids forbids in the state behind the row's path, and
+                         the per-row committed state they start from (guide=; no counterpart)
   tree_commit / tree_commit_stochastic   end of a round at temperature 0 / > 0  llama_glide.py:1093-1121
   linear / linear_multi / mlp_gate_up   the projections of a decode pass (M <= 80 token rows):
                          q/k/v/o_proj llama.py:361-363,390, LlamaMLP (qwen2.py:218-230), lm_head llama_glide.py:1091
@@ -699,6 +701,87 @@ def ban_rows(logits: torch.Tensor, table: torch.Tensor, output_ids: Optional[tor
                                    BAN_TABLE_WORDS, out_p, out_sb, W, _len_i32(base, b, "base"), _len_i32(base_sub, b, "base_sub"),
                                    int(base_add), ids_p, ids_sb, mask_p, mask_sb, mask_sr, C, _stream()), "ls_ban_rows")
     return logits
+
+
+GUIDE_HEADER_WORDS = 8     # int32 words in front of a guide table's class area (longspec_amd/guide.py, LS_GUIDE_HEADER_WORDS)
+GUIDE_MAX_EXTRA = 128      # columns of extra_ids, and ids per guide_advance (LS_GUIDE_MAX_EXTRA)
+GUIDE_SLICE = 8192         # ids per workgroup of guide_rows (LS_GUIDE_SLICE)
+
+
+def _guide_table(table, who):
+    if table.dtype != torch.int32 or table.dim() != 1 or table.numel() < GUIDE_HEADER_WORDS or not table.is_contiguous() \
+            or table.data_ptr() % 16 != 0:
+        raise TypeError(f"{who}: table must be a contiguous, 16-byte aligned int32 tensor of at least {GUIDE_HEADER_WORDS} words "
+                        "(Guide.table)")
+    return table.data_ptr(), table.numel()
+
+
+def guide_rows(logits: torch.Tensor, table: torch.Tensor, state: torch.Tensor, extra_ids: Optional[torch.Tensor] = None,
+               extra_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Guided decoding on TARGET logits [b, V] or [b, R, V] (16-bit, unit column stride, any non-overlapping row strides), IN
+    PLACE (``ls_guide_rows``, one launch; the definition is ``longspec_amd/guide.py``).  Row r of batch z is in the state
+    ``state[z]`` (int32 [b], the state behind the committed text) walked along every ``extra_ids[z, c]`` (int64 [b, C]) with
+    ``extra_mask[z, r, c] != 0`` (int64 [b, R, C], or [R, C] = one mask for the whole batch) in increasing ``c``.  A dead row
+    (state -1) keeps its bits; in a live one every token without a transition in ``table`` (``Guide.table``) becomes -inf and
+    every other element keeps its bits.  The grid is sized from V: nothing is read back.  Returns ``logits``."""
+    _dev(logits, table, state, extra_ids, extra_mask)
+    if logits.dim() not in (2, 3) or logits.dtype not in (torch.float16, torch.bfloat16) or logits.stride(-1) != 1:
+        raise TypeError("guide_rows: logits must be fp16 / bf16 [b, V] or [b, R, V] with unit column stride")
+    x = logits if logits.dim() == 3 else logits.unsqueeze(1)
+    b, R, V = x.shape
+    if (R > 1 and x.stride(1) < V) or (b > 1 and x.stride(0) < V):
+        raise ValueError("guide_rows: overlapping rows")
+    tab_p, tab_n = _guide_table(table, "guide_rows")
+    if state.dtype != torch.int32 or tuple(state.shape) != (b,) or not state.is_contiguous():
+        raise TypeError(f"guide_rows: state must be a contiguous int32 [{b}] tensor")
+    C = 0
+    ids_p = mask_p = None
+    ids_sb = mask_sb = mask_sr = 0
+    if extra_ids is not None and extra_ids.shape[-1] > 0:
+        if extra_mask is None:
+            raise ValueError("guide_rows: extra_ids needs extra_mask")
+        C = extra_ids.shape[-1]
+        if C > GUIDE_MAX_EXTRA:
+            raise ValueError(f"guide_rows: {C} extra columns, at most {GUIDE_MAX_EXTRA}")
+        if extra_ids.dtype != torch.int64 or extra_ids.dim() != 2 or extra_ids.shape[0] != b or extra_ids.stride(1) != 1:
+            raise TypeError("guide_rows: extra_ids must be int64 [b, C] with contiguous rows")
+        if extra_mask.dtype != torch.int64 or extra_mask.dim() not in (2, 3) or extra_mask.stride(-1) != 1 \
+                or tuple(extra_mask.shape[-2:]) != (R, C) or (extra_mask.dim() == 3 and extra_mask.shape[0] != b):
+            raise TypeError("guide_rows: extra_mask must be int64 [b, R, C] or [R, C] with unit column stride")
+        ids_p, ids_sb = extra_ids.data_ptr(), extra_ids.stride(0)
+        mask_p, mask_sr = extra_mask.data_ptr(), extra_mask.stride(-2)
+        mask_sb = extra_mask.stride(0) if extra_mask.dim() == 3 else 0
+    elif extra_mask is not None and extra_ids is None:
+        raise ValueError("guide_rows: extra_mask needs extra_ids")
+    _C.check(_C.load().ls_guide_rows(x.data_ptr(), b, R, V, _dtype(x), x.stride(0), max(x.stride(1), V), tab_p, tab_n,
+                                     state.data_ptr(), ids_p, ids_sb, mask_p, mask_sb, mask_sr, C, _stream()), "ls_guide_rows")
+    return logits
+
+
+def guide_advance(state: torch.Tensor, table: torch.Tensor, ids: torch.Tensor, num: Optional[torch.Tensor] = None) -> None:
+    """Advance the guide state [b] int32 in place (``ls_guide_advance``): ``state[z]`` walks every ``ids[z, j]`` (int64 [b, n],
+    n <= 128) with ``j < num[z]`` (``num`` [b] int64, None: all) through ``table`` (``Guide.table``).  An id outside the
+    vocabulary or without a transition leaves -1, and -1 stays -1."""
+    _dev(state, table, ids, num)
+    if state.dtype != torch.int32 or state.dim() != 1 or not state.is_contiguous():
+        raise TypeError("guide_advance: state must be a contiguous int32 [b] tensor")
+    b = state.shape[0]
+    tab_p, tab_n = _guide_table(table, "guide_advance")
+    if ids.dim() == 1:
+        ids = ids.view(b, -1)
+    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] != b:
+        raise TypeError("guide_advance: ids must be int64 [b, n]")
+    if not (1 <= ids.shape[1] <= GUIDE_MAX_EXTRA):
+        raise ValueError(f"guide_advance: {ids.shape[1]} ids per row, 1..{GUIDE_MAX_EXTRA}")
+    if ids.shape[1] > 1 and ids.stride(1) != 1:
+        ids = ids.contiguous()
+    num_p, num_s = None, 0
+    if num is not None:
+        if num.dtype != torch.int64 or num.numel() != b or num.dim() != 1:
+            raise TypeError("guide_advance: num must be int64 [b]")
+        num_p, num_s = num.data_ptr(), num.stride(0)
+    _C.check(_C.load().ls_guide_advance(state.data_ptr(), b, tab_p, tab_n, ids.data_ptr(), ids.shape[1], ids.stride(0), num_p, num_s,
+                                        _stream()), "ls_guide_advance")
 
 
 _ngram_ws = _Workspace()     # its own buffer, as _sample_ws: a captured round holds its address
