@@ -359,6 +359,37 @@ int ls_sample_rows(const void* logits, int rows, int vocab, int64_t ld, int dtyp
                    float* out_top2_key, int32_t* out_kept, float* out_threshold, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* ls_sample_rows with two more filters.  Order: top_k -> top_p -> min_p -> typical_p, each on the set the former kept.
+ *   min_p in [0, 1] (0 = off): keep j iff exp((x_j - x_max) / temperature) >= min_p.
+ *   typical_p in (0, 1] (1 = off), locally typical sampling on the set S kept so far: with a(v) = (x_max - v) / temperature,
+ *     q(v) = exp(-a(v)) / Z over S and A = sum q a (the entropy is ln Z + A, the surprise of v is ln Z + a(v)), the distance of
+ *     v is d(v) = |a(v) - A|; d* is the smallest distance with sum of q over {d(v) <= d*} >= typical_p and {j in S : d(x_j) <= d*}
+ *     is kept, ties at d* included.  The kept values are a contiguous run [lo, hi] of S's values; the maximum may be dropped.
+ * out_threshold [rows] = the smallest kept finite value, out_upper [rows] (optional) = the largest (-inf for a row without a
+ * finite logit), out_kept = the kept count.  With min_p = 0 and typical_p = 1 the launches and every output bit are those of
+ * ls_sample_rows.  Everything else -- the draw, the keying, alignment, the independence of the rows -- as ls_sample_rows.
+ * LS_ERR_INVALID_ARG: as ls_sample_rows, and min_p outside [0, 1] or typical_p outside (0, 1]. */
+typedef struct ls_sample_desc {
+    const void* logits;          /* [rows, vocab] dtype, row stride ld                                   */
+    const int64_t* positions;    /* [rows]                                                               */
+    const int32_t* streams;      /* [rows] or NULL (= 0)                                                 */
+    int64_t* out_idx;            /* [rows]                                                               */
+    int64_t* out_top2_idx;       /* [rows, 2] or NULL                                                    */
+    float* out_top2_key;         /* [rows, 2] or NULL                                                    */
+    int32_t* out_kept;           /* [rows] or NULL                                                       */
+    float* out_threshold;        /* [rows] or NULL                                                       */
+    float* out_upper;            /* [rows] or NULL                                                       */
+    int64_t ld;
+    uint64_t seed;
+    int32_t rows, vocab, dtype, top_k;
+    float temperature, top_p, min_p, typical_p;
+} ls_sample_desc;
+
+/* Scratch for ls_sample_rows_ex: ls_sample_workspace_bytes plus, with typical_p < 1, 768 KiB per row (counts and prefix sums
+ * of the 2^16 values; fully rewritten by every call, no clearing needed). */
+size_t ls_sample_ex_workspace_bytes(const ls_sample_desc* d);
+int ls_sample_rows_ex(const ls_sample_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Token penalties and a logit bias on TARGET logits, in front of ls_argmax_rows / ls_sample_rows (csrc/penalty.hip; no counterpart
  * in the reference).  state [b, vocab] int32 (batch stride state_stride_b): bits 0-30 of a word = times the token was generated
  * (first token included), bit 31 = the token occurs in the valid part of the prompt.  logits / out [b, rows, vocab] dtype with

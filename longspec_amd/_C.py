@@ -54,6 +54,18 @@ class LinearDesc(C.Structure):
     ]
 
 
+class SampleDesc(C.Structure):
+    """Mirror of ``ls_sample_desc`` (include/longspec_hip.h) -- keep field order in sync."""
+    _fields_ = [
+        ("logits", C.c_void_p), ("positions", C.c_void_p), ("streams", C.c_void_p), ("out_idx", C.c_void_p),
+        ("out_top2_idx", C.c_void_p), ("out_top2_key", C.c_void_p), ("out_kept", C.c_void_p), ("out_threshold", C.c_void_p),
+        ("out_upper", C.c_void_p),
+        ("ld", C.c_int64), ("seed", C.c_uint64),
+        ("rows", C.c_int32), ("vocab", C.c_int32), ("dtype", C.c_int32), ("top_k", C.c_int32),
+        ("temperature", C.c_float), ("top_p", C.c_float), ("min_p", C.c_float), ("typical_p", C.c_float),
+    ]
+
+
 # every symbol include/longspec_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int
@@ -93,6 +105,8 @@ SYMBOLS = {
     "ls_sample_workspace_bytes": (C.c_size_t, [_I, _I]),
     "ls_sample_rows": (C.c_int, [_P, _I, _I, _L, _I, _P, _P, C.c_uint64, C.c_float, _I, C.c_float, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                  _P]),
+    "ls_sample_ex_workspace_bytes": (C.c_size_t, [C.POINTER(SampleDesc)]),
+    "ls_sample_rows_ex": (C.c_int, [C.POINTER(SampleDesc), _P, C.c_size_t, _P]),
     "ls_penalize_rows": (C.c_int, [_P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _L, _P, _L, _P, _L, _L, _I, C.c_float, C.c_float,
                                    C.c_float, _P, _P]),
     "ls_token_state_add": (C.c_int, [_P, _I, _I, _L, _P, _I, _L, _P, _L, _I, _P]),

@@ -21,73 +21,21 @@
 //                         smallest kept value
 //   sample_merge_kernel   one thread per row: the row's two best over its chunks, outputs
 // Filters off: the last two launches only.  top-k: + 4.  top-p: + 6 (the first pair finds x_max).
-#include "ls_common.h"
+//
+// ls_sample_rows_ex adds min_p (one more lower bound) and typical_p (a band [lower, upper] of values that may exclude the
+// maximum): their kernels are in sample_band.hip and run between the selections above and the key pass, which honours
+// `upper` as well as `lower` and reports the largest kept value.  With both off the launches are the ones listed here.
+#include "sample_common.h"
 
 namespace {
 
-constexpr int SM_THREADS = 256;
-constexpr int SM_CHUNK = 8192;          // logits per workgroup: 32 per thread
-constexpr int SM_REC_WORDS = 8;         // candidate record of (row, chunk), 32-bit words: best (2), second (2), finite kept, -inf kept, min kept, pad
+constexpr int SM_REC_WORDS = 8;         // candidate record of (row, chunk), 32-bit words: best (2), second (2), finite kept, -inf kept, min kept, max kept
 
-struct RowState {
-    unsigned lower;                     // ordered 16-bit key: logits below it take no part (0 = all)
-    unsigned bin;                       // level 0 result: the high byte that holds the target
-    unsigned long long target;          // what is left of the target inside `bin`
-    float m;                            // row maximum
-    unsigned pad[3];
-};
-
-__device__ __forceinline__ unsigned order_key(unsigned bits16) {       // as topk.hip: -0.0 and +0.0 share 0x8000
-    return (bits16 & 0x8000u) ? 0x8000u - (bits16 & 0x7fffu) : (bits16 | 0x8000u);
-}
 __device__ __forceinline__ unsigned order_key32(float f) {
     const unsigned b = __float_as_uint(f);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ __forceinline__ float key32_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-struct Philox {
-    unsigned w[4];
-};
-__device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return Philox{{c0, c1, c2, c3}};
-}
-
-// the 32 logits of a thread: element e = j*8 + i sits at column col0[j] + i
-template <typename E>
-struct Chunk {
-    uint32_t raw[16];
-    int col0[4];
-    int V;
-    __device__ __forceinline__ void load(const typename E::T* src, int base, int V_, int tid) {
-        V = V_;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int c = base + (j * SM_THREADS + tid) * 8;
-            col0[j] = c;
-            uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (c < V) v = *reinterpret_cast<const uint4*>(src + c);                       // V % 8 == 0: all-in or all-out
-            raw[j * 4 + 0] = v.x; raw[j * 4 + 1] = v.y; raw[j * 4 + 2] = v.z; raw[j * 4 + 3] = v.w;
-        }
-    }
-    __device__ __forceinline__ unsigned bits(int e) const { return (raw[e >> 1] >> ((e & 1) * 16)) & 0xffffu; }
-    __device__ __forceinline__ float val(int e) const {
-        const unsigned short h = (unsigned short)bits(e);
-        return E::to_f32(__builtin_bit_cast(typename E::T, h));
-    }
-    __device__ __forceinline__ bool valid(int e) const { return col0[e >> 3] < V; }
-};
 
 // mode 0: weight 1; mode 1: weight F(x).  level 0: bin = high byte; level 1: low byte of the logits whose high byte is st.bin
 template <typename E>
@@ -178,6 +126,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_select_kernel(int level, in
     if (level == 0 && mode == 0 && tid == 0) {
         state[row].m = fmaxf(fmaxf(s_cm[0], s_cm[1]), fmaxf(s_cm[2], s_cm[3]));
         state[row].lower = 0u;
+        state[row].upper = 0xffffu;
     }
     if (total == 0ull) {
         if (tid == 0 && level == 0) { state[row].bin = 0u; state[row].target = 0ull; }
@@ -213,17 +162,18 @@ __global__ __launch_bounds__(SM_THREADS) void sample_key_kernel(const typename E
                                                                 const RowState* __restrict__ state, unsigned* __restrict__ cand) {
     __shared__ unsigned long long s_b[8];
     __shared__ int s_n[8];
-    __shared__ float s_min[4];
+    __shared__ float s_min[4], s_max[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int chunk = blockIdx.x, row = blockIdx.y, nchunks = gridDim.x;
     Chunk<E> ck;
     ck.load(logits + (long)row * ld, chunk * SM_CHUNK, V, tid);
     const unsigned lower = filtered ? state[row].lower : 0u;
+    const unsigned upper = filtered ? state[row].upper : 0xffffu;
     const unsigned long long pos = (unsigned long long)positions[row];
     const unsigned strm = streams ? (unsigned)streams[row] : 0u;
     unsigned long long b1 = 0ull, b2 = 0ull;             // (ordered fp32 key << 32) | ~column
     int n_fin = 0, n_inf = 0;
-    float vmin = INFINITY;
+    float vmin = INFINITY, vmax = -INFINITY;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {                        // 4 consecutive columns share one Philox block
         const int c = ck.col0[q >> 1] + (q & 1) * 4;
@@ -232,7 +182,8 @@ __global__ __launch_bounds__(SM_THREADS) void sample_key_kernel(const typename E
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int e = q * 4 + i;
-            if (order_key(ck.bits(e)) < lower) continue;
+            const unsigned k16 = order_key(ck.bits(e));
+            if (k16 < lower || k16 > upper) continue;
             const float x = ck.val(e);
             const float u = ((float)(r.w[i] >> 9) + 0.5f) * 1.1920928955078125e-07f;       // 2^-23: exact, in (0, 1)
             const float key = x / T - logf(-logf(u));
@@ -240,7 +191,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_key_kernel(const typename E
             if (pk > b1) { b2 = b1; b1 = pk; }
             else if (pk > b2) b2 = pk;
             if (x == -INFINITY) ++n_inf;
-            else { ++n_fin; vmin = fminf(vmin, x); }
+            else { ++n_fin; vmin = fminf(vmin, x); vmax = fmaxf(vmax, x); }
         }
     }
 #pragma unroll
@@ -249,11 +200,13 @@ __global__ __launch_bounds__(SM_THREADS) void sample_key_kernel(const typename E
         n_fin += __shfl_xor(n_fin, off);
         n_inf += __shfl_xor(n_inf, off);
         vmin = fminf(vmin, __shfl_xor(vmin, off));
+        vmax = fmaxf(vmax, __shfl_xor(vmax, off));
     }
     if (lane == 0) {
         s_b[wave * 2] = b1; s_b[wave * 2 + 1] = b2;
         s_n[wave * 2] = n_fin; s_n[wave * 2 + 1] = n_inf;
         s_min[wave] = vmin;
+        s_max[wave] = vmax;
     }
     __syncthreads();
     if (tid == 0) {
@@ -262,30 +215,32 @@ __global__ __launch_bounds__(SM_THREADS) void sample_key_kernel(const typename E
             n_fin += s_n[w * 2];
             n_inf += s_n[w * 2 + 1];
             vmin = fminf(vmin, s_min[w]);
+            vmax = fmaxf(vmax, s_max[w]);
         }
         unsigned* rec = cand + ((long)row * nchunks + chunk) * SM_REC_WORDS;
         rec[0] = (unsigned)b1; rec[1] = (unsigned)(b1 >> 32);
         rec[2] = (unsigned)b2; rec[3] = (unsigned)(b2 >> 32);
         rec[4] = (unsigned)n_fin; rec[5] = (unsigned)n_inf;
-        rec[6] = __float_as_uint(vmin); rec[7] = 0u;
+        rec[6] = __float_as_uint(vmin); rec[7] = __float_as_uint(vmax);
     }
 }
 
 __global__ __launch_bounds__(SM_THREADS) void sample_merge_kernel(const unsigned* __restrict__ cand, int rows, int nchunks,
                                                                   int64_t* __restrict__ out_idx, int64_t* __restrict__ top2_idx,
                                                                   float* __restrict__ top2_key, int32_t* __restrict__ out_kept,
-                                                                  float* __restrict__ out_thr) {
+                                                                  float* __restrict__ out_thr, float* __restrict__ out_upper) {
     const int row = blockIdx.x * SM_THREADS + threadIdx.x;
     if (row >= rows) return;
     unsigned long long b1 = 0ull, b2 = 0ull;
     long n_fin = 0, n_inf = 0;
-    float vmin = INFINITY;
+    float vmin = INFINITY, vmax = -INFINITY;
     for (int c = 0; c < nchunks; ++c) {
         const unsigned* rec = cand + ((long)row * nchunks + c) * SM_REC_WORDS;
         top2_merge(b1, b2, ((unsigned long long)rec[1] << 32) | rec[0], ((unsigned long long)rec[3] << 32) | rec[2]);
         n_fin += rec[4];
         n_inf += rec[5];
         vmin = fminf(vmin, __uint_as_float(rec[6]));
+        vmax = fmaxf(vmax, __uint_as_float(rec[7]));
     }
     // -inf logits (key -inf) only count while the row has no finite logit at all
     const long kept = n_fin > 0 ? n_fin : n_inf;
@@ -301,6 +256,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_merge_kernel(const unsigned
     }
     if (out_kept) out_kept[row] = (int32_t)kept;
     if (out_thr) out_thr[row] = n_fin > 0 ? vmin : -INFINITY;
+    if (out_upper) out_upper[row] = vmax;                // -inf for a row without a finite logit
 }
 
 struct SampleWs {
@@ -317,31 +273,28 @@ SampleWs sample_ws(int rows, int vocab) {
     return w;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t ls_sample_workspace_bytes(int rows, int vocab) {
-    if (rows < 1 || vocab < 8) return 0;
-    return sample_ws(rows, vocab).total;
-}
-
-int ls_sample_rows(const void* logits, int rows, int vocab, int64_t ld, int dtype, const int64_t* positions, const int32_t* streams,
-                   uint64_t seed, float temperature, int top_k, float top_p, int64_t* out_idx, int64_t* out_top2_idx,
-                   float* out_top2_key, int32_t* out_kept, float* out_threshold, void* workspace, size_t workspace_bytes,
-                   void* stream) {
-    if (!logits || !positions || !out_idx || !workspace) LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows: null pointer");
-    if (dtype != LS_F16 && dtype != LS_BF16) LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows: dtype");
+// Both entry points: d.min_p = 0 and d.typical_p = 1 issue the launches of ls_sample_rows and nothing else.
+int sample_run(const ls_sample_desc& d, void* workspace, size_t workspace_bytes, void* stream, const char* who) {
+    const void* logits = d.logits;
+    const int rows = d.rows, vocab = d.vocab, dtype = d.dtype, top_k = d.top_k;
+    const int64_t ld = d.ld;
+    const float temperature = d.temperature, top_p = d.top_p;
+    if (!logits || !d.positions || !d.out_idx || !workspace) LS_FAIL(LS_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (dtype != LS_F16 && dtype != LS_BF16) LS_FAIL(LS_ERR_INVALID_ARG, "%s: dtype", who);
     if (rows < 1 || rows > 65535 || vocab < 8 || vocab > (1 << 24) || vocab % 8 != 0 || ld < vocab || ld % 8 != 0)
-        LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows: rows=%d vocab=%d ld=%ld (vocab and ld must be multiples of 8, rows <= 65535, "
-                "vocab <= 2^24)", rows, vocab, (long)ld);
+        LS_FAIL(LS_ERR_INVALID_ARG, "%s: rows=%d vocab=%d ld=%ld (vocab and ld must be multiples of 8, rows <= 65535, "
+                "vocab <= 2^24)", who, rows, vocab, (long)ld);
     if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f) || !(top_p <= 1.f))
-        LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows: temperature=%g (> 0), top_k=%d (>= 0), top_p=%g (0 < p <= 1)", (double)temperature,
+        LS_FAIL(LS_ERR_INVALID_ARG, "%s: temperature=%g (> 0), top_k=%d (>= 0), top_p=%g (0 < p <= 1)", who, (double)temperature,
                 top_k, (double)top_p);
+    if (!(d.min_p >= 0.f) || !(d.min_p <= 1.f) || !(d.typical_p > 0.f) || !(d.typical_p <= 1.f))
+        LS_FAIL(LS_ERR_INVALID_ARG, "%s: min_p=%g (0 <= min_p <= 1), typical_p=%g (0 < typical_p <= 1)", who, (double)d.min_p,
+                (double)d.typical_p);
     if (reinterpret_cast<uintptr_t>(logits) % 16 != 0 || reinterpret_cast<uintptr_t>(workspace) % 16 != 0)
-        LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows: logits and workspace must be 16-byte aligned");
+        LS_FAIL(LS_ERR_INVALID_ARG, "%s: logits and workspace must be 16-byte aligned", who);
     const SampleWs w = sample_ws(rows, vocab);
-    if (workspace_bytes < w.total) LS_FAIL(LS_ERR_WORKSPACE, "ls_sample_rows: workspace too small");
+    const bool use_k = top_k > 0 && top_k < vocab, use_p = top_p < 1.f, use_m = d.min_p > 0.f, use_t = d.typical_p < 1.f;
+    if (workspace_bytes < w.total + (use_t ? ls_sample_band_bytes(rows) : 0)) LS_FAIL(LS_ERR_WORKSPACE, "%s: workspace too small", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* base = static_cast<char*>(workspace);
     RowState* state = reinterpret_cast<RowState*>(base + w.state);
@@ -350,7 +303,6 @@ int ls_sample_rows(const void* logits, int rows, int vocab, int64_t ld, int dtyp
     float* cmax = reinterpret_cast<float*>(base + w.cmax);
     const int nchunks = (vocab + SM_CHUNK - 1) / SM_CHUNK;
     const dim3 grid(nchunks, rows), block(SM_THREADS);
-    const bool use_k = top_k > 0 && top_k < vocab, use_p = top_p < 1.f;
     auto hist_pass = [&](int level, int mode) -> int {
         if (dtype == LS_F16)
             hipLaunchKernelGGL(sample_hist_kernel<ElemF16>, grid, block, 0, s, static_cast<const _Float16*>(logits), (long)ld, vocab,
@@ -365,26 +317,64 @@ int ls_sample_rows(const void* logits, int rows, int vocab, int64_t ld, int dtyp
         return LS_OK;
     };
     int rc;
-    if (use_k || use_p) {
-        if ((rc = hist_pass(0, 0))) return rc;           // also the row maximum and lower = 0
+    const int filtered = (use_k || use_p || use_m || use_t) ? 1 : 0;
+    if (filtered) {
+        if ((rc = hist_pass(0, 0))) return rc;           // also the row maximum, lower = 0 and upper = 0xffff
         if (use_k && (rc = hist_pass(1, 0))) return rc;
         if (use_p) {
             if ((rc = hist_pass(0, 1))) return rc;
             if ((rc = hist_pass(1, 1))) return rc;
         }
+        if (use_m && (rc = ls_sample_minp_launch(rows, dtype, temperature, d.min_p, state, s))) return rc;
+        if (use_t && (rc = ls_sample_band_launch(logits, rows, vocab, (long)ld, dtype, temperature, d.typical_p, state,
+                                                 base + w.total, s)))
+            return rc;
     }
-    const int filtered = (use_k || use_p) ? 1 : 0;
+    const unsigned seed_lo = (unsigned)d.seed, seed_hi = (unsigned)(d.seed >> 32);
     if (dtype == LS_F16)
         hipLaunchKernelGGL(sample_key_kernel<ElemF16>, grid, block, 0, s, static_cast<const _Float16*>(logits), (long)ld, vocab,
-                           positions, streams, (unsigned)seed, (unsigned)(seed >> 32), temperature, filtered, state, cand);
+                           d.positions, d.streams, seed_lo, seed_hi, temperature, filtered, state, cand);
     else
         hipLaunchKernelGGL(sample_key_kernel<ElemBF16>, grid, block, 0, s, static_cast<const __bf16*>(logits), (long)ld, vocab,
-                           positions, streams, (unsigned)seed, (unsigned)(seed >> 32), temperature, filtered, state, cand);
+                           d.positions, d.streams, seed_lo, seed_hi, temperature, filtered, state, cand);
     LS_CHECK_LAUNCH("sample_key_kernel");
-    hipLaunchKernelGGL(sample_merge_kernel, dim3((rows + SM_THREADS - 1) / SM_THREADS), block, 0, s, cand, rows, nchunks, out_idx,
-                       out_top2_idx, out_top2_key, out_kept, out_threshold);
+    hipLaunchKernelGGL(sample_merge_kernel, dim3((rows + SM_THREADS - 1) / SM_THREADS), block, 0, s, cand, rows, nchunks, d.out_idx,
+                       d.out_top2_idx, d.out_top2_key, d.out_kept, d.out_threshold, d.out_upper);
     LS_CHECK_LAUNCH("sample_merge_kernel");
     return LS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ls_sample_workspace_bytes(int rows, int vocab) {
+    if (rows < 1 || vocab < 8) return 0;
+    return sample_ws(rows, vocab).total;
+}
+
+size_t ls_sample_ex_workspace_bytes(const ls_sample_desc* d) {
+    if (!d || d->rows < 1 || d->vocab < 8) return 0;
+    return sample_ws(d->rows, d->vocab).total + (d->typical_p < 1.f ? ls_sample_band_bytes(d->rows) : 0);
+}
+
+int ls_sample_rows(const void* logits, int rows, int vocab, int64_t ld, int dtype, const int64_t* positions, const int32_t* streams,
+                   uint64_t seed, float temperature, int top_k, float top_p, int64_t* out_idx, int64_t* out_top2_idx,
+                   float* out_top2_key, int32_t* out_kept, float* out_threshold, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+    ls_sample_desc d = {};
+    d.logits = logits; d.positions = positions; d.streams = streams;
+    d.out_idx = out_idx; d.out_top2_idx = out_top2_idx; d.out_top2_key = out_top2_key;
+    d.out_kept = out_kept; d.out_threshold = out_threshold; d.out_upper = nullptr;
+    d.ld = ld; d.seed = seed;
+    d.rows = rows; d.vocab = vocab; d.dtype = dtype; d.top_k = top_k;
+    d.temperature = temperature; d.top_p = top_p; d.min_p = 0.f; d.typical_p = 1.f;
+    return sample_run(d, workspace, workspace_bytes, stream, "ls_sample_rows");
+}
+
+int ls_sample_rows_ex(const ls_sample_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!d) LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows_ex: null descriptor");
+    return sample_run(*d, workspace, workspace_bytes, stream, "ls_sample_rows_ex");
 }
 
 }  // extern "C"

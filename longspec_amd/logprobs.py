@@ -7,8 +7,8 @@ target logits ``x`` as the token was picked from them -- behind the penalties wh
 
     lp_j = (x_j - m) / T - ln sum_i exp((x_i - m) / T),   m = max_i x_i
 
-The distribution is over the FULL vocabulary: a sampled token that survived a top-k / top-p cut is reported under the tempered,
-penalised soft-max, not under the renormalised kept set ("processed logits, not truncated") -- the one definition that is the
+The distribution is over the FULL vocabulary: a sampled token that survived a top-k / top-p / min_p / typical_p cut is reported
+under the tempered, penalised soft-max, not under the renormalised kept set ("processed logits, not truncated") -- the one definition that is the
 same for greedy and sampled rows.  The alternatives are the ``top_n`` columns with the largest logits, ordered by (logit
 descending, column ascending): the order of the arg-max, so under greedy decoding the first alternative IS the emitted token.
 

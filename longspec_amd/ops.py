@@ -11,7 +11,7 @@ One function per reference seam of the draft-then-verify round:
   lse_merge              N-way form of llama.py:385-387,420 for sequence-sharded prefix KV
   logprob_topk / argmax_rows   beam growth and greedy verification on the lm_head logits  llama_glide.py:1019-1064,1091
                          (logp_out=: the draft's log-prob table of the temperature > 0 rounds, :1025,1074)
-  sample_rows            one draw per row from the target's tempered, top-k / top-p filtered distribution (sampling=;
+  sample_rows            one draw per row from the target's tempered, top-k / top-p / min_p / typical_p filtered distribution (sampling=;
                          no counterpart in the reference)
   penalize_rows / token_state_add   repetition / presence / frequency penalties and a logit bias on the target's logits, per
                          row from that row's own history, and the [batch, vocab] state they read (penalties=; no counterpart)
@@ -372,13 +372,15 @@ _sample_ws = _Workspace()    # its own buffer: a captured round holds its addres
 
 
 def sample_rows(logits: torch.Tensor, positions: torch.Tensor, sampling, streams: Optional[torch.Tensor] = None,
-                return_top2: bool = False):
+                return_top2: bool = False, return_upper: bool = False):
     """One draw per row of lm_head outputs [..., V] from soft-max(x / T) under ``sampling``'s top-k / top-p
-    (``ls_sample_rows``): int64 [...].  ``positions`` [...] int64 = absolute position of the token each row PREDICTS FROM
+    (``ls_sample_rows``) and, where the object has them switched on, min_p / typical_p (``ls_sample_rows_ex``): int64 [...].  ``positions`` [...] int64 = absolute position of the token each row PREDICTS FROM
     (the position fed to RoPE for that row), ``streams`` [...] int32 = its batch row (None: 0) -- with the seed they key the
     noise, so a position draws the same noise in every loop.  ``return_top2``: also (top2_idx [..., 2], top2_key [..., 2],
-    kept [...] int32, threshold [...] fp32)."""
+    kept [...] int32, threshold [...] fp32 = the smallest kept value); ``return_upper`` appends upper [...] fp32, the largest
+    kept value (below the row maximum where typical_p dropped it)."""
     _dev(logits, positions, streams)
+    min_p, typical_p = float(getattr(sampling, "min_p", 0.0)), float(getattr(sampling, "typical_p", 1.0))
     shape = logits.shape[:-1]
     V = logits.shape[-1]
     x = logits.reshape(-1, V)
@@ -395,22 +397,37 @@ def sample_rows(logits: torch.Tensor, positions: torch.Tensor, sampling, streams
             raise ValueError(f"sample_rows: {n} rows of logits, {strm.numel()} streams")
     dev = logits.device
     out = torch.empty((n,), dtype=torch.int64, device=dev)
-    t2i = t2k = kept = thr = None
+    t2i = t2k = kept = thr = upper = None
+    if return_upper:
+        upper = torch.empty((n,), dtype=torch.float32, device=dev)
     if return_top2:
         t2i = torch.empty((n, 2), dtype=torch.int64, device=dev)
         t2k = torch.empty((n, 2), dtype=torch.float32, device=dev)
         kept = torch.empty((n,), dtype=torch.int32, device=dev)
         thr = torch.empty((n,), dtype=torch.float32, device=dev)
     lib = _C.load()
-    need = lib.ls_sample_workspace_bytes(n, V)
-    ws = _sample_ws.get(dev, max(need, 1))
     ptr = lambda t: t.data_ptr() if t is not None else None
-    _C.check(lib.ls_sample_rows(x.data_ptr(), n, V, x.stride(0), _dtype(x), pos.data_ptr(), ptr(strm), sampling.seed,
-                                sampling.temperature, sampling.top_k, sampling.top_p, out.data_ptr(), ptr(t2i), ptr(t2k), ptr(kept),
-                                ptr(thr), ws.data_ptr(), ws.numel(), _stream()), "ls_sample_rows")
+    if min_p == 0.0 and typical_p == 1.0 and not return_upper:
+        need = lib.ls_sample_workspace_bytes(n, V)
+        ws = _sample_ws.get(dev, max(need, 1))
+        _C.check(lib.ls_sample_rows(x.data_ptr(), n, V, x.stride(0), _dtype(x), pos.data_ptr(), ptr(strm), sampling.seed,
+                                    sampling.temperature, sampling.top_k, sampling.top_p, out.data_ptr(), ptr(t2i), ptr(t2k),
+                                    ptr(kept), ptr(thr), ws.data_ptr(), ws.numel(), _stream()), "ls_sample_rows")
+    else:
+        d = _C.SampleDesc(logits=x.data_ptr(), positions=pos.data_ptr(), streams=ptr(strm), out_idx=out.data_ptr(),
+                          out_top2_idx=ptr(t2i), out_top2_key=ptr(t2k), out_kept=ptr(kept), out_threshold=ptr(thr),
+                          out_upper=ptr(upper), ld=x.stride(0), seed=sampling.seed, rows=n, vocab=V, dtype=_dtype(x),
+                          top_k=sampling.top_k, temperature=sampling.temperature, top_p=sampling.top_p, min_p=min_p,
+                          typical_p=typical_p)
+        need = lib.ls_sample_ex_workspace_bytes(C.byref(d))
+        ws = _sample_ws.get(dev, max(need, 1))
+        _C.check(lib.ls_sample_rows_ex(C.byref(d), ws.data_ptr(), ws.numel(), _stream()), "ls_sample_rows_ex")
+    res = (out.view(shape),)
     if return_top2:
-        return out.view(shape), t2i.view(*shape, 2), t2k.view(*shape, 2), kept.view(shape), thr.view(shape)
-    return out.view(shape)
+        res += (t2i.view(*shape, 2), t2k.view(*shape, 2), kept.view(shape), thr.view(shape))
+    if return_upper:
+        res += (upper.view(shape),)
+    return res if len(res) > 1 else res[0]
 
 
 def penalize_rows(logits: torch.Tensor, state: torch.Tensor, penalties, extra_ids: Optional[torch.Tensor] = None,

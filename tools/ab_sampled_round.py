@@ -4,6 +4,10 @@ temperature > 0 round alternate, all replayed from HIP graphs, on the synthetic-
 16k-token prefix, tree 4 16 16 16 16).  Writes profiles/sampled_round_ab.json.
 
     python tools/ab_sampled_round.py [--blocks 6] [--per 15] [--sampling t=0.6,k=50,p=0.95,seed=1]
+                                     [--more t=0.6,m=0.05,seed=1 --more t=0.6,typ=0.9,seed=1]
+
+``--more SPEC`` adds a further sampled arm (named ``sampled[SPEC]``) to the interleaving: the min_p and typical_p rounds are
+held against the ``sampled`` arm (top-k / top-p, the launches of ``ls_sample_rows``) of the same run.
 
 Each figure is a host clock around `per` rounds that end in a device synchronise; the spread is what the blocks of ONE arm
 differ by on this box in this run, the yardstick for the difference between the arms.  The three arms keep their own decode
@@ -31,6 +35,7 @@ def main():
     ap.add_argument("--blocks", type=int, default=6)
     ap.add_argument("--per", type=int, default=15)
     ap.add_argument("--sampling", default="t=0.6,k=50,p=0.95,seed=1")
+    ap.add_argument("--more", action="append", default=[], help="a further sampled arm, a LONGSPEC_SAMPLING string")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sampled_round_ab.json"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "a measurement needs the GPU"
@@ -49,7 +54,9 @@ def main():
     first = torch.tensor([1000], dtype=torch.int64, device=dev)
     random.seed(99)
     torch.manual_seed(99)
-    t = {a: [] for a in ARMS}
+    more = {f"sampled[{spec}]": Sampling.parse(spec) for spec in args.more}
+    arms = ARMS + tuple(more)
+    t = {a: [] for a in arms}
 
     def one_round(arm, st):
         if arm != "stochastic":
@@ -66,6 +73,8 @@ def main():
         states = {"greedy": m.begin_tree_decode(first, lens, PREFIX, bench.TREE, max_gen, eos_id=-1),
                   "sampled": m.begin_tree_decode(first, lens, PREFIX, bench.TREE, max_gen, eos_id=-1, sampling=sampling),
                   "stochastic": m.begin_tree_decode(first, lens, PREFIX, bench.TREE, max_gen, eos_id=-1, temperature=TEMPERATURE)}
+        for arm, s in more.items():
+            states[arm] = m.begin_tree_decode(first, lens, PREFIX, bench.TREE, max_gen, eos_id=-1, sampling=s)
         assert states["greedy"].sampling is None, "unset LONGSPEC_SAMPLING: the greedy arm must be greedy"
         for arm, st in states.items():                 # every shape an arm uses, and the captures, before the clock
             st.eos = None
@@ -96,7 +105,7 @@ def main():
         return {"median_ms": v[len(v) // 2], "min_ms": v[0], "max_ms": v[-1], "blocks_ms": [round(x, 4) for x in v],
                 "spread": (v[-1] - v[0]) / v[len(v) // 2]}
 
-    res = {a: stats(t[a]) for a in ARMS}
+    res = {a: stats(t[a]) for a in arms}
     spread = max(r["spread"] for r in res.values())
     g = res["greedy"]["median_ms"]
     out = {"what": "ms per tree round replayed from HIP graphs: greedy, sampled (sampling=) and the reference-style temperature > 0 "
@@ -105,7 +114,8 @@ def main():
            "sampling": repr(sampling), "stochastic_temperature": TEMPERATURE, "rounds_per_block": per,
            "device": torch.cuda.get_device_name(0), **res, "same_box_spread": spread,
            "sampled_over_greedy": res["sampled"]["median_ms"] / g, "stochastic_over_greedy": res["stochastic"]["median_ms"] / g,
-           "sampled_within_2_percent_of_greedy": res["sampled"]["median_ms"] <= g * 1.02}
+           "sampled_within_2_percent_of_greedy": res["sampled"]["median_ms"] <= g * 1.02,
+           "more_over_sampled": {a: res[a]["median_ms"] / res["sampled"]["median_ms"] for a in more}}
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
