@@ -30,6 +30,8 @@ import os
 
 import torch
 
+from .keyword import resolve_keyword
+
 BAN_ENV = "LONGSPEC_BAN"         # "seq=13+13|198+198+198,ngram=4": the process-wide default
 MAX_SEQS = 64
 MAX_SEQ_LEN = 16
@@ -137,13 +139,7 @@ def env_ban():
 
 def resolve(ban, temperature, use_env: bool):
     """The ``Ban`` a loop runs with: the argument; else, where `use_env` and no temperature is given, the default."""
-    if ban is not None:
-        if not isinstance(ban, Ban):
-            raise TypeError(f"ban must be a longspec_amd.Ban or None, got {type(ban).__name__}")
-        if temperature is not None and temperature > 0:
-            raise ValueError("ban= is not available with temperature > 0, the reference's own T > 0 path; sampled decoding "
-                             "with banned tokens is sampling= with ban=")
-        return ban
-    if use_env and not temperature:
-        return env_ban()
-    return None
+    return resolve_keyword(ban, Ban, "ban", env_ban,
+                           "is not available with temperature > 0, the reference's own T > 0 path; sampled decoding "
+                           "with banned tokens is sampling= with ban=",
+                           temperature, use_env)

@@ -36,6 +36,8 @@ import os
 import numpy as np
 import torch
 
+from .keyword import resolve_keyword
+
 GUIDE_ENV = "LONGSPEC_GUIDE"     # path of a Guide.save() file: the process-wide default
 MAX_CLASSES = 16384              # C (LS_GUIDE_MAX_CLASSES): a state's allow bits are at most 2 KB
 MAX_CELLS = 1 << 24              # S * C (LS_GUIDE_MAX_CELLS): the transition area is at most 64 MB
@@ -298,13 +300,7 @@ def env_guide():
 
 def resolve(guide, temperature, use_env: bool):
     """The ``Guide`` a loop runs with: the argument; else, where `use_env` and no temperature is given, the default."""
-    if guide is not None:
-        if not isinstance(guide, Guide):
-            raise TypeError(f"guide must be a longspec_amd.Guide or None, got {type(guide).__name__}")
-        if temperature is not None and temperature > 0:
-            raise ValueError("guide= is not available with temperature > 0, the reference's own T > 0 path; sampled decoding "
-                             "under a guide is sampling= with guide=")
-        return guide
-    if use_env and not temperature:
-        return env_guide()
-    return None
+    return resolve_keyword(guide, Guide, "guide", env_guide,
+                           "is not available with temperature > 0, the reference's own T > 0 path; sampled decoding "
+                           "under a guide is sampling= with guide=",
+                           temperature, use_env)

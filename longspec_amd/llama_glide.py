@@ -22,12 +22,7 @@ import torch
 from torch import nn
 
 from .graphs import GraphReplayer
-from .sampling import resolve as _resolve_sampling
-from .penalties import resolve as _resolve_penalties
-from .logprobs import new_buffers as _logprob_buffers, resolve as _resolve_logprobs
-from .stop import new_state as _stop_state, resolve as _resolve_stop, result_of as _stop_result
-from .ban import resolve as _resolve_ban
-from .guide import resolve as _resolve_guide
+from .target_rules import TargetRules
 from .lookup import check as _lookup_check
 from .llama import (DecodeLinear, LlamaForCausalLM, LlamaMLP, LlamaRMSNorm, chunked_causal_prefill,
                     project_qkv, _default_ops)
@@ -347,146 +342,10 @@ class LlamaGlide(LlamaForCausalLM):
             position_ids = torch.arange(ids.size(1), device=ids.device)[None, :] + pos_base[:, None] + pos_add
         return hidden_states, None, self.model.rotary_emb(hidden_states, position_ids)
 
-    def _target_tokens(self, logits, sampling, positions, streams=None):
-        """The target's token for every row of ``logits`` [bsz, (rows,) V]: the arg-max, or with ``sampling`` one draw per row
-        (``ops.sample_rows``) keyed by ``positions`` -- the positions RoPE saw for those rows -- and the batch row."""
-        if sampling is None:
-            return self.ops.argmax_rows(logits)
-        bsz = logits.size(0)
-        if streams is None and bsz > 1:
-            streams = torch.arange(bsz, device=logits.device, dtype=torch.int32)
-        if streams is not None and logits.dim() == 3:
-            streams = streams.view(bsz, 1).expand(bsz, logits.size(1))
-        return self.ops.sample_rows(logits, positions, sampling, streams=streams)
-
-    def _token_state(self, bsz: int, device, prompt_ids=None, prompt_len=None):
-        """A fresh penalty state [bsz, V] int32 (``penalties.py``): bit 31 of a word = the token occurs in
-        ``prompt_ids[z, :prompt_len[z]]`` (``prompt_ids=None``: no flags, the synthetic-KV benchmark case), bits 0-30 (times
-        generated) zero."""
-        state = torch.zeros((bsz, self.lm_head.out_features), dtype=torch.int32, device=device)
-        if prompt_ids is not None:
-            num = None
-            if prompt_len is not None:
-                num = prompt_len.to(device=device, dtype=torch.int64).view(-1).expand(bsz).contiguous()
-            self.ops.token_state_add(state, prompt_ids.to(device=device, dtype=torch.int64), num=num, prompt=True)
-        return state
-
-    def _begin_penalties(self, st, penalties, bsz: int, device, prompt_ids, prompt_len, first_token, prompt_state=None):
-        """The penalty part of a decode state: ``st.penalties`` (resolved), ``st.token_state`` = the prompt's flags
-        (``prompt_state`` when the caller has built them already, for the first token) with ``first_token`` counted, and
-        ``st.bias_table``, the dense fp32 [V] bias on the device -- put there now, nothing is copied inside a graph capture.
-        Refused under a vocabulary-parallel shard."""
-        st.penalties, st.token_state, st.bias_table = penalties, None, None
-        if penalties is None:
-            return
-        sh = self.model.layers[-1].self_attn.shard
-        if sh is not None and sh.vocab_parallel:
-            raise ValueError("penalties= is not available with a vocabulary-parallel shard")
-        st.token_state = prompt_state if prompt_state is not None else self._token_state(bsz, device, prompt_ids, prompt_len)
-        self.ops.token_state_add(st.token_state, first_token.to(device=device, dtype=torch.int64).view(bsz, 1))
-        st.bias_table = penalties.bias_table(self.lm_head.out_features, device)
-
-    def _begin_logprobs(self, st, logprobs, bsz: int, width: int, device, first=None):
-        """The log-prob part of a decode state: ``st.logprobs`` = None, or the namespace of ``logprobs.py`` -- ``token``
-        [bsz, width], ``top_ids`` / ``top`` [bsz, width, top_n], aligned column for column with ``st.output_ids`` and holding
-        their fill values -- plus ``top_n`` and ``temperature``, the sampler's (1 for greedy decoding).  ``first``: the rows of
-        the first token (``_first_token``), written to column 0; None (a caller that starts from synthetic caches): column 0
-        keeps the fill.  Refused under a vocabulary-parallel shard."""
-        st.logprobs = None
-        if logprobs is None:
-            return
-        sh = self.model.layers[-1].self_attn.shard
-        if sh is not None and sh.vocab_parallel:
-            raise ValueError("logprobs= is not available with a vocabulary-parallel shard")
-        lp = _logprob_buffers(bsz, width, logprobs.top_n, device)
-        lp.top_n = logprobs.top_n
-        lp.temperature = st.sampling.temperature if st.sampling is not None else 1.0
-        if first is not None:
-            lp.token[:, 0], lp.top[:, 0], lp.top_ids[:, 0] = first[0][:, 0], first[1][:, 0], first[2][:, 0]
-        st.logprobs = lp
-
-    def _begin_stop(self, st, stop, bsz: int, device, table=None):
-        """The stop part of a decode state: ``st.stop`` = None, or a namespace of ``cfg`` (the ``Stop``), ``table`` (its int32
-        device table, ``table`` when the caller has built it already, for the first token) and ``min_tokens``;
-        ``st.stop_state`` [bsz, 4] int32 = (length, which, match_start, reserved), -1 while nothing has stopped;
-        ``st.last_stop`` = the namespace the loops publish (views of it); ``st.stopped`` = the host's copy of "a round reported
-        a stop".  ``min_tokens > 0`` is refused under a vocabulary-parallel shard: no rank holds a whole row of logits there."""
-        st.stop, st.stop_state, st.last_stop, st.stopped = None, None, None, False
-        if stop is None:
-            return
-        sh = self.model.layers[-1].self_attn.shard
-        if stop.min_tokens > 0 and sh is not None and sh.vocab_parallel:
-            raise ValueError("stop= with min_tokens > 0 is not available with a vocabulary-parallel shard")
-        if table is None:
-            table = stop.table(self.lm_head.out_features, device)
-        st.stop = SimpleNamespace(cfg=stop, table=table, min_tokens=stop.min_tokens)
-        st.stop_state = _stop_state(bsz, device)
-        st.last_stop = _stop_result(st.stop_state)
-
-    def _begin_ban(self, st, ban, device, table=None):
-        """The ban part of a decode state: ``st.ban`` = None, or a namespace of ``cfg`` (the ``Ban``) and ``table`` (its int32
-        device table, ``table`` when the caller has built it already, for the first token) -- put there now, nothing is copied
-        inside a graph capture.  The ban needs no state beyond ``st.output_ids``.  Refused under a vocabulary-parallel shard: no
-        rank holds a whole row of logits there."""
-        st.ban = None
-        if ban is None:
-            return
-        sh = self.model.layers[-1].self_attn.shard
-        if sh is not None and sh.vocab_parallel:
-            raise ValueError("ban= is not available with a vocabulary-parallel shard")
-        if table is None:
-            table = ban.table(self.lm_head.out_features, device)
-        st.ban = SimpleNamespace(cfg=ban, table=table)
-
-    def _begin_guide(self, st, guide, bsz: int, device, first_token, table=None):
-        """The guide part of a decode state: ``st.guide`` = None, or a namespace of ``cfg`` (the ``Guide``), ``table`` (its int32
-        device table, ``table`` when the caller has built it already, for the first token -- built now, never inside a graph
-        capture) and ``state``, int32 [bsz]: the automaton's state behind the committed text, here ``start`` advanced by
-        ``first_token``; ``ops.guide_advance`` moves it behind every commit.  Like the penalty state it is not rolled back by
-        ``stop=``.  Refused under a vocabulary-parallel shard: no rank holds a whole row of logits there."""
-        st.guide = None
-        if guide is None:
-            return
-        sh = self.model.layers[-1].self_attn.shard
-        if sh is not None and sh.vocab_parallel:
-            raise ValueError("guide= is not available with a vocabulary-parallel shard")
-        if table is None:
-            table = guide.table(self.lm_head.out_features, device)
-        state = torch.full((bsz,), guide.start, dtype=torch.int32, device=device)
-        self.ops.guide_advance(state, table, first_token.to(device=device, dtype=torch.int64).view(bsz, 1))
-        st.guide = SimpleNamespace(cfg=guide, table=table, state=state)
-
-    def _stop_scan(self, st, written, written_sub=None, written_add=0, num=None, fill=0, state=None):
-        """``ops.stop_scan`` on a decode state: the columns this round (``num`` per row; None: one) wrote to ``st.output_ids``,
-        erasing ``st.spec_mask`` and ``st.logprobs`` along with it where the state has them."""
-        self.ops.stop_scan(st.output_ids, st.stop.table, st.stop_state, written, written_sub=written_sub, written_add=written_add,
-                           num=num, fill=fill, state=state, spec_mask=getattr(st, "spec_mask", None), logprobs=st.logprobs)
-
-    def _first_token(self, logits, sampling, input_len, penalties=None, prompt_state=None, logprobs=None, stop=None,
-                     stop_table=None, ban_table=None, guide=None, guide_table=None):
-        """The prefill's token from ``logits`` [bsz, V] of prompt row ``input_len - 1``; under ``penalties`` the history of
-        that row is the prompt alone (``prompt_state``: ``_token_state`` of the prompt); under a ``stop`` with ``min_tokens > 0``
-        the stop ids of ``stop_table`` are banned from it (column 0); under ``ban_table`` (``Ban.table``) the one-token sequences
-        are (its text is empty); under ``guide`` with ``guide_table`` (``Guide.table``) the tokens without a transition from
-        ``guide.start`` are.  Returns (token, its log-prob rows
-        (``ops.token_logprobs``) under ``logprobs``, else None)."""
-        if penalties is not None:
-            logits = self.ops.penalize_rows(logits, prompt_state, penalties)
-        if stop is not None and stop.min_tokens > 0:
-            logits = self.ops.stop_ban_rows(logits, stop_table)
-        if ban_table is not None:
-            logits = self.ops.ban_rows(logits, ban_table, None)
-        if guide is not None:
-            start = torch.full((logits.size(0),), guide.start, dtype=torch.int32, device=logits.device)
-            logits = self.ops.guide_rows(logits, guide_table, start)
-        if sampling is None:
-            token = logits.argmax(dim=-1)
-        else:
-            positions = input_len.to(device=logits.device, dtype=torch.int64).view(-1) - 1
-            token = self._target_tokens(logits, sampling, positions)
-        if logprobs is None:
-            return token, None
-        return token, self.ops.token_logprobs(logits, token, sampling.temperature if sampling is not None else 1.0, logprobs.top_n)
+    def _rules(self, device, temperature, shard, head_sharded=False, **keywords):
+        """The ``TargetRules`` (``target_rules.py``) of a loop on this model from its six request ``keywords``: resolved,
+        refused or built -- tables included -- before any forward."""
+        return TargetRules(self.ops, self.lm_head.out_features, device, temperature, shard, head_sharded, **keywords)
 
     def _stop_id(self, eos_id, loop: str):
         """Token whose appearance ends a loop.  The Llama twin tests ``self.config.eos_token_id`` in all
@@ -512,31 +371,15 @@ class LlamaGlide(LlamaForCausalLM):
     @torch.inference_mode()
     def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645, sampling=None,
                          penalties=None, logprobs=None, stop=None, ban=None, guide=None):                                      # :552-585
-        """``sampling`` (``longspec_amd.Sampling``): every token is drawn from the target's filtered distribution instead of
-        taken as its arg-max -- the denominator of a sampled speculative run, and with the same seed the same text.
-        ``penalties`` (``longspec_amd.Penalties``): the logits of every step are penalised from the prompt and the text so far.
-        ``logprobs`` (``longspec_amd.Logprobs``): the log-prob of every token under the distribution it was taken from and its
-        top-n alternatives, published as ``self.last_logprobs`` (``logprobs.py``; None without it); the return tuple is
-        unchanged.
-        ``stop`` (``longspec_amd.Stop``): a row ends at its first stop match (``stop.py``): its columns behind the match go
-        back to 0, the loop ends when every row has stopped (tested where the EOS test is, every 16th step) and the elapsed
-        time is cut back to the step of the last row's stop.  The result is ``self.last_stop`` (None without it).  The built-in
-        EOS test runs alongside, unchanged.  ``num``, the KV lengths and the penalty state are not rolled back: they describe
-        the steps that ran, ``last_stop.length`` is the authority on the text.
-        ``ban`` (``longspec_amd.Ban``): banned sequences and no-repeat n-grams (``ban.py``): the tokens the text so far forbids
-        are -inf in every step's logits, behind the penalties and in front of the arg-max or draw and the log-probs.
-        ``guide`` (``longspec_amd.Guide``): guided decoding (``guide.py``): the tokens without a transition from the state behind
-        the text so far are -inf in every step's logits, at the same place; the state advances behind every token."""
+        """``sampling`` / ``penalties`` / ``logprobs`` / ``stop`` / ``ban`` / ``guide``: the rules on the target's logits
+        (``target_rules.py``), on every step's one row; with ``sampling`` this loop is the denominator of a sampled speculative
+        run, and with the same seed the same text.  The log-probs are published as ``self.last_logprobs``, the stop result as
+        ``self.last_stop`` (None without the keyword); the return tuple is unchanged.  Under ``stop`` the loop ends when every
+        row has stopped (tested where the EOS test is, every 16th step) and the elapsed time is cut back to the step of the
+        last row's stop; the built-in EOS test runs alongside, unchanged."""
         assert input_ids is not None, "please give the input"
-        sampling = _resolve_sampling(sampling, None, use_env=True)
-        pen = _resolve_penalties(penalties, None, use_env=True)
-        lpc = _resolve_logprobs(logprobs, None, use_env=True)
-        stp = _resolve_stop(stop, None, use_env=True)
-        stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
-        bn = _resolve_ban(ban, None, use_env=True)
-        btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
-        gd = _resolve_guide(guide, None, use_env=True)
-        gtab = gd.table(self.lm_head.out_features, input_ids.device) if gd is not None else None
+        rules = self._rules(input_ids.device, None, None, sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop,
+                            ban=ban, guide=guide)
         self._clear_shard()
         bsz = input_ids.size(0)
         output_ids = input_ids.new_zeros((bsz, max_gen_len))
@@ -547,9 +390,7 @@ class LlamaGlide(LlamaForCausalLM):
         hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
         input_len = prompt_length
         rows = torch.arange(bsz, device=input_ids.device)
-        pstate = self._token_state(bsz, input_ids.device, input_ids, input_len) if pen is not None else None
-        output_ids[:, 0], first_lp = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), sampling, input_len,
-                                                       pen, pstate, lpc, stp, stab, btab, gd, gtab)
+        output_ids[:, 0] = rules.first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), input_len, input_ids)
         cache_lens += input_len.int()
         num = 0
         eos = self._stop_id(eos_id, "vanilla")
@@ -560,9 +401,7 @@ class LlamaGlide(LlamaForCausalLM):
         if on_gpu:
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record()
-        vs = self.begin_vanilla_decode(output_ids, cache_lens, input_len.int(), P, sampling=sampling, penalties=penalties,
-                                       prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp,
-                                       stop=stop, stop_table=stab, ban=ban, ban_table=btab, guide=guide, guide_table=gtab)
+        vs = self.begin_vanilla_decode(output_ids, cache_lens, input_len.int(), P, prompt_ids=input_ids, rules=rules)
         self.last_logprobs = vs.logprobs
         self.last_stop = vs.last_stop
         for step in range(1, max_gen_len):
@@ -604,40 +443,20 @@ class LlamaGlide(LlamaForCausalLM):
 
     # ------------------------------------------------------------------------------------------
     def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int, sampling=None, penalties=None,
-                             prompt_ids=None, prompt_state=None, logprobs=None, first_logprobs=None, stop=None, stop_table=None,
-                             ban=None, ban_table=None, guide=None, guide_table=None):
+                             prompt_ids=None, logprobs=None, stop=None, ban=None, guide=None, rules=None):
         """State of the vanilla loop (``llama_glide.py:566-583``): ``output_ids`` [bsz, max_gen] with the first
-        token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32.  ``sampling``:
-        draw instead of arg-max (None: the process-wide default LONGSPEC_SAMPLING, else greedy).  ``penalties``: penalise
-        every step's logits (None: the process-wide default LONGSPEC_PENALTIES, else none) from ``vs.token_state``, which
-        starts from ``prompt_ids[z, :input_len[z]]`` (None: no prompt flags; ``prompt_state``: those flags, already built)
-        and the first token.  ``logprobs``: every step also fills its column of ``vs.logprobs`` (None: the process-wide
-        default LONGSPEC_LOGPROBS, else none; ``first_logprobs``: the first token's rows, for column 0).  ``stop``: every step
-        tests its column against the stops (``stop.py``; None: the process-wide default LONGSPEC_STOP, else none;
-        ``stop_table``: its device table, already built) and keeps ``vs.stop_state`` / ``vs.last_stop``; column 0 is tested
-        here.  A row that has stopped keeps decoding with the batch, and every step erases what it wrote; KV lengths and the
-        penalty state are not rolled back.  ``ban``: every step's logits carry -inf where the text so far forbids a token
-        (``ban.py``; None: the process-wide default LONGSPEC_BAN, else none; ``ban_table``: its device table, already built).
-        ``guide``: every step's logits carry -inf where the automaton has no transition from ``vs.guide.state``, which starts
-        from the first token and advances behind every step (``guide.py``; None: the process-wide default LONGSPEC_GUIDE, else
-        none; ``guide_table``: its device table, already built)."""
+        token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32.  The six keywords:
+        ``target_rules.py`` (``rules``: the ``TargetRules`` the caller has built from them already, for the first token);
+        ``prompt_ids[z, :input_len[z]]`` is the prompt the penalty state starts from (None: no prompt flags).  Every step rules
+        its one row, which predicts column ``cache_lens - input_len + 1``.  A row that has stopped keeps decoding with the
+        batch, and every step erases what it wrote."""
         dev = output_ids.device
-        sampling = _resolve_sampling(sampling, None, use_env=True)
-        penalties = _resolve_penalties(penalties, None, use_env=True)
-        logprobs = _resolve_logprobs(logprobs, None, use_env=True)
-        stop = _resolve_stop(stop, None, use_env=True)
-        ban = _resolve_ban(ban, None, use_env=True)
-        guide = _resolve_guide(guide, None, use_env=True)
+        if rules is None:
+            rules = self._rules(dev, None, self.model.layers[-1].self_attn.shard, sampling=sampling, penalties=penalties,
+                                logprobs=logprobs, stop=stop, ban=ban, guide=guide)
         vs = _DecodeState(output_ids=output_ids, cache_lens=cache_lens, input_len=input_len, P=prompt_bound, step=0,
-                          rows=torch.arange(output_ids.size(0), device=dev), sampling=sampling, penalties=penalties)
-        self._begin_penalties(vs, penalties, output_ids.size(0), dev, prompt_ids, input_len, output_ids[:, 0], prompt_state)
-        self._begin_logprobs(vs, logprobs, output_ids.size(0), output_ids.size(1), dev, first_logprobs)
-        self._begin_stop(vs, stop, output_ids.size(0), dev, stop_table)
-        self._begin_ban(vs, ban, dev, ban_table)
-        self._begin_guide(vs, guide, output_ids.size(0), dev, output_ids[:, 0], guide_table)
-        if vs.stop is not None:
-            self._stop_scan(vs, cache_lens, input_len, 1)
-        vs.streams = torch.arange(output_ids.size(0), device=dev, dtype=torch.int32) if sampling is not None else None
+                          rows=torch.arange(output_ids.size(0), device=dev))
+        rules.bind(vs, output_ids[:, 0], prompt_ids, input_len, (cache_lens, input_len, 1, 0))
         vs.use_graphs = bool(dev.type == "cuda" and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
         P = prompt_bound                                   # (the replayer holds no reference to the state that holds it)
         vs.replayer = GraphReplayer(self, lambda bound: (P + bound, P + bound), output_ids.size(1), "vanilla step")
@@ -645,32 +464,17 @@ class LlamaGlide(LlamaForCausalLM):
 
     def _vanilla_device(self, vs):
         """One token, device work only: the step has no host-side parameter at all."""
-        out, cl, il, rows = vs.output_ids, vs.cache_lens, vs.input_len, vs.rows
+        out, cl, il, rows, rules = vs.output_ids, vs.cache_lens, vs.input_len, vs.rows, vs.rules
         cur = out[rows, (cl - il).long()].view(out.size(0), -1)
         hidden_states = self.model.forward(cur, cache_lens=cl, exec_type="decoding").last_hidden_state
+        logits = rules.apply(self.lm_head(hidden_states[:, -1, :]))
         # (sampling: the row was rotated to position cl, the length before this step's increment)
-        logits = self.lm_head(hidden_states[:, -1, :])
-        if vs.penalties is not None:
-            logits = self.ops.penalize_rows(logits, vs.token_state, vs.penalties, bias=vs.bias_table)
-        if vs.stop is not None and vs.stop.min_tokens > 0:    # the row predicts column cl - il + 1
-            logits = self.ops.stop_ban_rows(logits, vs.stop.table, base=cl, base_sub=il, base_add=1)
-        if vs.ban is not None:                                # the text so far: columns 0 .. cl - il
-            logits = self.ops.ban_rows(logits, vs.ban.table, out, base=cl, base_sub=il, base_add=1)
-        if vs.guide is not None:                              # the state behind columns 0 .. cl - il
-            logits = self.ops.guide_rows(logits, vs.guide.table, vs.guide.state)
-        llm_output = self._target_tokens(logits, vs.sampling, cl, vs.streams)
+        llm_output = rules.tokens(logits, cl)
+        pending = rules.pending(logits, llm_output)          # the token's row -> the column it is about to be written to
         cl += 1
         out[rows, (cl - il).long()] = llm_output.view(-1)
-        if vs.logprobs is not None:                          # the token's row -> the column it was written to
-            lp = vs.logprobs
-            self.ops.logprob_commit(self.ops.token_logprobs(logits, llm_output.view(-1), lp.temperature, lp.top_n), lp,
-                                    (cl - il).to(torch.int32))
-        if vs.penalties is not None:
-            self.ops.token_state_add(vs.token_state, llm_output.view(out.size(0), 1))
-        if vs.guide is not None:
-            self.ops.guide_advance(vs.guide.state, vs.guide.table, llm_output.view(out.size(0), 1))
-        if vs.stop is not None:
-            self._stop_scan(vs, cl, il, 1)
+        rules.record(pending)
+        rules.advance(llm_output.view(out.size(0), 1))
 
     def vanilla_step(self, vs):
         """Decode one token.  On a GPU the step is captured into a HIP graph after GRAPH_AFTER eager steps and replayed."""
@@ -720,15 +524,8 @@ class LlamaGlide(LlamaForCausalLM):
     def _chain_generate(self, input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter, sampling=None,
                         penalties=None, logprobs=None, stop=None, ban=None, guide=None):
         assert input_ids is not None, "please give the input"
-        sampling = _resolve_sampling(sampling, temperature, use_env=True)
-        pen = _resolve_penalties(penalties, temperature, use_env=True)
-        lpc = _resolve_logprobs(logprobs, temperature, use_env=True)
-        stp = _resolve_stop(stop, temperature, use_env=True)
-        stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
-        bn = _resolve_ban(ban, temperature, use_env=True)
-        btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
-        gd = _resolve_guide(guide, temperature, use_env=True)
-        gtab = gd.table(self.lm_head.out_features, input_ids.device) if gd is not None else None
+        rules = self._rules(input_ids.device, temperature, None, sampling=sampling, penalties=penalties, logprobs=logprobs,
+                            stop=stop, ban=ban, guide=guide)
         magic = drafter == "magicdec"      # (temperature > 0: the same rejection block in both loops, :715-736 = :854-875)
         self._clear_shard()
         bsz = input_ids.size(0)
@@ -750,12 +547,9 @@ class LlamaGlide(LlamaForCausalLM):
             position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=cache_lens.clone(), llm_kv_len=cache_lens.clone(), exec_type="prefill")
-        pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
-        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab, btab, gd, gtab)
+        first = rules.first_token(logits, input_len, input_ids)
         st = self.begin_chain_decode(first, cache_lens, input_len, P, gamma, max_gen_len, eos_id, temperature, drafter,
-                                     first_logits=logits, sampling=sampling, penalties=penalties, prompt_ids=input_ids,
-                                     prompt_state=pstate, logprobs=logprobs, first_logprobs=first_lp, stop=stop, stop_table=stab,
-                                     ban=ban, ban_table=btab, guide=guide, guide_table=gtab)
+                                     first_logits=logits, prompt_ids=input_ids, rules=rules)
         self.last_logprobs = st.logprobs
         self.last_stop = st.last_stop
         _sync(input_ids)
@@ -769,50 +563,25 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_chain_decode(self, first_token, cache_lens, input_len, prompt_bound: int, gamma=4, max_gen_len=64, eos_id=151645,
                            temperature=0.0, drafter="glide", first_logits=None, sampling=None, penalties=None, prompt_ids=None,
-                           prompt_state=None, logprobs=None, first_logprobs=None, stop=None, stop_table=None, ban=None,
-                           ban_table=None, guide=None, guide_table=None):
+                           logprobs=None, stop=None, ban=None, guide=None, rules=None):
         """State of the chain-speculation loop right after the prefills (``llama_glide.py:641-668``): ``first_token`` [bsz]
         = the target's first generated token, ``cache_lens`` [bsz] int32 = valid rows of every cache (the draft's included),
         ``input_len`` [bsz] = prompt length, ``prompt_bound`` = host-side bound of it.  Also the entry point of benchmarks
-        that time ``chain_round`` on synthetic KV (bench.py --method seq).  ``sampling``: the verification pass draws its
-        tokens instead of taking arg-maxes (None at temperature 0: the process-wide default LONGSPEC_SAMPLING, else greedy);
-        the drafter stays greedy.  ``penalties``: the verification rows are penalised, row i from ``st.token_state`` (the prompt
-        ``prompt_ids[z, :input_len[z]]``, None: no prompt flags, and the text so far) plus the i draft tokens it follows; the
-        drafter stays unpenalised.  ``logprobs``: the rows a round accepts fill their columns of ``st.logprobs`` (None at
-        temperature 0: the process-wide default LONGSPEC_LOGPROBS, else none; ``first_logprobs``: the first token's rows).
-        ``stop``: every round tests the columns it wrote against the stops (``stop.py``; None at temperature 0: the process-wide
-        default LONGSPEC_STOP, else none; ``stop_table``: its device table, already built) inside the round, in front of its one
-        host read; a match ends the loop with that round, the columns of ``output_ids`` / ``spec_mask`` / ``st.logprobs`` behind
-        it go back to their fill and ``st.last_stop`` holds (length, which, match_start).  KV lengths, ``st.token_state`` and the
-        host counters ``count`` / ``num`` / ``emitted`` are not rolled back: a stopped state is final.  ``ban``: verification row
-        i carries -inf where the text so far plus the i draft tokens it follows forbid a token (``ban.py``; None at temperature
-        0: the process-wide default LONGSPEC_BAN, else none; ``ban_table``: its device table, already built); the drafter stays
-        unbanned.  ``guide``: verification row i carries -inf where the automaton has no transition from ``st.guide.state`` (the
-        state behind the text so far, advanced behind every commit) walked along the i draft tokens it follows; a row whose
-        draft tokens leave the language keeps its bits and is never accepted (``guide.py``; None at temperature 0: the
-        process-wide default LONGSPEC_GUIDE, else none; ``guide_table``: its device table, already built); the drafter stays
-        unguided."""
+        that time ``chain_round`` on synthetic KV (bench.py --method seq).  The six keywords: ``target_rules.py`` (``rules``:
+        the ``TargetRules`` the caller has built from them already); ``prompt_ids[z, :input_len[z]]`` is the prompt the penalty
+        state starts from (None: no prompt flags).  A round rules the gamma + 1 verification rows: row i follows the text so
+        far plus the i draft tokens in front of it and predicts column ``cache_lens - input_len + 1 + i``; the rows a round
+        accepts fill their log-prob columns.  A ``stop=`` match ends the loop with that round; the host counters ``count`` /
+        ``num`` / ``emitted`` are not rolled back."""
         bsz = first_token.size(0)
         dev = first_token.device
-        sampling = _resolve_sampling(sampling, temperature, use_env=True)
-        penalties = _resolve_penalties(penalties, temperature, use_env=True)
-        logprobs = _resolve_logprobs(logprobs, temperature, use_env=True)
-        stop = _resolve_stop(stop, temperature, use_env=True)
-        ban = _resolve_ban(ban, temperature, use_env=True)
-        guide = _resolve_guide(guide, temperature, use_env=True)
+        if rules is None:
+            rules = self._rules(dev, temperature, self.model.layers[-1].self_attn.shard, sampling=sampling, penalties=penalties,
+                                logprobs=logprobs, stop=stop, ban=ban, guide=guide)
         if drafter != "magicdec":
             self._head_of_draft_passes()                # the draft passes' head and its pack exist before the first round
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
-                             max_gen_len=max_gen_len, count=0, num=0, emitted=1, double_flag=False, sampling=sampling)
-        st.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if sampling is not None else None
-        self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
-        self._begin_ban(st, ban, dev, ban_table)
-        self._begin_guide(st, guide, bsz, dev, first_token, guide_table)
-        st.chain_mask = None
-        if penalties is not None or st.ban is not None or st.guide is not None:
-            # verification row i follows the draft tokens spec_buffer[:, 1 : i + 1]
-            st.chain_mask = torch.ones((gamma + 1, gamma), dtype=torch.int64, device=dev).tril(-1)
-        self._begin_logprobs(st, logprobs, bsz, max_gen_len + gamma, dev, first_logprobs)
+                             max_gen_len=max_gen_len, count=0, num=0, emitted=1, double_flag=False)
         st.output_ids = first_token.new_zeros((bsz, max_gen_len + gamma))
         st.spec_mask = first_token.new_zeros((bsz, max_gen_len + gamma))
         st.output_ids[:, 0] = first_token
@@ -832,9 +601,7 @@ class LlamaGlide(LlamaForCausalLM):
         st.next_spec_start_token[:, 0] = st.output_ids[:, 0]
         st.eos = self._stop_id(eos_id, "spec")
         st.stream_rows = self.model.layers[0].self_attn.STREAM_SINK + self.model.layers[0].self_attn.STREAM_WINDOW
-        self._begin_stop(st, stop, bsz, dev, stop_table)
-        if st.stop is not None:                              # column 0; a hit ends the loop with its first round
-            self._stop_scan(st, st.cache_lens, st.input_len_i32, 1)
+        rules.bind(st, first_token, prompt_ids, input_len, (st.cache_lens, st.input_len_i32, 1, 0), gamma=gamma)
         return st
 
     def chain_round(self, st) -> bool:
@@ -889,46 +656,7 @@ class LlamaGlide(LlamaForCausalLM):
                 spec_buffer[:, spec_steps + 1] = self.ops.argmax_rows(current_logp).view(-1,)
                 if spec_logits is not None:
                     spec_logits[:, spec_steps + 1, :] = current_logp
-        hidden_states = self.model.forward(spec_buffer, cache_lens=cache_lens, exec_type="decoding").last_hidden_state
-        llm_verify_logits = self.lm_head(hidden_states[:, -gamma - 1:, :])
-        if st.penalties is not None:
-            llm_verify_logits = self.ops.penalize_rows(llm_verify_logits, st.token_state, st.penalties, spec_buffer[:, 1:],
-                                                       st.chain_mask, bias=st.bias_table)
-        if st.stop is not None and st.stop.min_tokens > 0:   # row i predicts column cache_lens - input_len + 1 + i
-            llm_verify_logits = self.ops.stop_ban_rows(llm_verify_logits, st.stop.table, base=cache_lens, base_sub=st.input_len_i32,
-                                                       base_add=1, depth="row")
-        if st.ban is not None:                               # row i: columns 0 .. cache_lens - input_len, then i draft tokens
-            llm_verify_logits = self.ops.ban_rows(llm_verify_logits, st.ban.table, output_ids, base=cache_lens,
-                                                  base_sub=st.input_len_i32, base_add=1, extra_ids=spec_buffer[:, 1:],
-                                                  extra_mask=st.chain_mask)
-        if st.guide is not None:                             # row i: the committed state walked along i draft tokens
-            llm_verify_logits = self.ops.guide_rows(llm_verify_logits, st.guide.table, st.guide.state,
-                                                    extra_ids=spec_buffer[:, 1:], extra_mask=st.chain_mask)
-        # (sampling: verification row i was rotated to position cache_lens + i, models' forward :571-577)
-        llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
-                                                cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
-        lp_rows = lp_base = None
-        if st.logprobs is not None:
-            # every verification row's token under the distribution it was taken from; the commit below keeps a prefix of
-            # them, at the columns behind cache_lens - input_len as it stands BEFORE chain_commit advances it
-            lp_rows = self.ops.token_logprobs(llm_verify_logits, llm_verify_output, st.logprobs.temperature, st.logprobs.top_n)
-            lp_base = (cache_lens - st.input_len_i32).to(torch.int32)
-        accept = None
-        if st.temperature > 0:                               # :715-736
-            llm_verify_output, accept = self.ops.chain_accept_stochastic(spec_logits, llm_verify_logits, spec_buffer,
-                                                                         llm_verify_output)
-        # acceptance by cumulative match, verified ids + bonus token -> output_ids, cache_lens += correct_len, the next
-        # round's start tokens and draft_cache_lens = cache_lens - double_input (:738-770): one launch, one host read
-        state = self.ops.chain_commit(llm_verify_output, spec_buffer, output_ids, cache_lens, draft_cache_lens, st.input_len_i32,
-                                      next_spec_start_token, st.eos, **({"accept_mask": accept} if accept is not None else {}))
-        if st.penalties is not None:                         # the correct_len tokens this round wrote, before the host read
-            self.ops.token_state_add(st.token_state, llm_verify_output, num=state[:, 0])
-        if st.guide is not None:                             # ... and the automaton follows them
-            self.ops.guide_advance(st.guide.state, st.guide.table, llm_verify_output, num=state[:, 0])
-        if lp_rows is not None:                              # ... and their log-probs, to the columns chain_commit wrote
-            self.ops.logprob_commit(lp_rows, st.logprobs, lp_base, base_add=1, num=state[:, 0])
-        if st.stop is not None:                              # the stop test on those columns; a hit rides in state[:, 1] (bit 1)
-            self._stop_scan(st, cache_lens, st.input_len_i32, 1, num=state[:, 0], state=state)
+        state = self._chain_verify(st, spec_logits)
         state = state.tolist()
         n_ok, hit = state[0][0], any(row[1] for row in state)
         st.stopped = any(row[1] & 2 for row in state)
@@ -949,7 +677,7 @@ class LlamaGlide(LlamaForCausalLM):
         tokens of prompt + output (``lookup.py``) -- verified exactly like ``spec_generate``.  No draft weights, no draft KV,
         no draft prefill and no draft pass: the glide layer is never called, so a model without a draft checkpoint can use
         it.  A round is one ``ops.ngram_draft`` and one (gamma + 1)-row target pass.  Same return tuple as ``spec_generate``;
-        ``sampling`` / ``penalties`` / ``logprobs`` / ``stop`` / ``ban`` act on the verification rows as they do there
+        ``sampling`` / ``penalties`` / ``logprobs`` / ``stop`` / ``ban`` / ``guide`` act on the verification rows as they do there
         (``self.last_logprobs``, ``self.last_stop``); ``self.last_lookup`` holds ``hist`` [bsz, max_ngram + 1] int64 -- how many
         rounds matched at which length, [:, 0] = none -- and ``info`` [bsz, 2] int32 = (n, e) of the last round, both on the
         device.  There is no ``temperature=``: the reference's T > 0 rejection needs the draft logits a lookup does not have.
@@ -963,15 +691,8 @@ class LlamaGlide(LlamaForCausalLM):
         the chain loop above, unchanged."""
         assert input_ids is not None, "please give the input"
         gamma, max_ngram, min_ngram = _lookup_check(gamma, max_ngram, min_ngram, branches)
-        sampling = _resolve_sampling(sampling, None, use_env=True)
-        pen = _resolve_penalties(penalties, None, use_env=True)
-        lpc = _resolve_logprobs(logprobs, None, use_env=True)
-        stp = _resolve_stop(stop, None, use_env=True)
-        stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
-        bn = _resolve_ban(ban, None, use_env=True)
-        btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
-        gd = _resolve_guide(guide, None, use_env=True)
-        gtab = gd.table(self.lm_head.out_features, input_ids.device) if gd is not None else None
+        rules = self._rules(input_ids.device, None, None, sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop,
+                            ban=ban, guide=guide)
         self._clear_shard()
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
@@ -984,12 +705,9 @@ class LlamaGlide(LlamaForCausalLM):
         rows = torch.arange(bsz, device=dev)
         logits = self.lm_head(hidden_states[rows, input_len - 1, :])
         cache_lens = input_ids.new_zeros((bsz)).int() + input_len.int()
-        pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
-        first, first_lp = self._first_token(logits, sampling, input_len, pen, pstate, lpc, stp, stab, btab, gd, gtab)
+        first = rules.first_token(logits, input_len, input_ids)
         st = self.begin_lookup_decode(first, cache_lens, input_len, P, input_ids, gamma, max_ngram, min_ngram, max_gen_len, eos_id,
-                                      sampling=sampling, penalties=penalties, prompt_state=pstate, logprobs=logprobs,
-                                      first_logprobs=first_lp, stop=stop, stop_table=stab, branches=branches, ban=ban,
-                                      ban_table=btab, guide=guide, guide_table=gtab)
+                                      branches=branches, rules=rules)
         self.last_logprobs = st.logprobs
         self.last_stop = st.last_stop
         self.last_lookup = st.last_lookup
@@ -1003,9 +721,8 @@ class LlamaGlide(LlamaForCausalLM):
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
     def begin_lookup_decode(self, first_token, cache_lens, input_len, prompt_bound: int, prompt_ids, gamma=7, max_ngram=3,
-                            min_ngram=1, max_gen_len=64, eos_id=151645, sampling=None, penalties=None, prompt_state=None,
-                            logprobs=None, first_logprobs=None, stop=None, stop_table=None, branches=1, ban=None,
-                            ban_table=None, guide=None, guide_table=None):
+                            min_ngram=1, max_gen_len=64, eos_id=151645, sampling=None, penalties=None, logprobs=None, stop=None,
+                            branches=1, ban=None, guide=None, rules=None):
         """State of the prompt-lookup loop right after the target's prefill: the arguments of ``begin_chain_decode`` that have
         a meaning without a drafter, plus ``prompt_ids`` [bsz, P] -- here not optional: ``prompt_ids[z, :input_len[z]]`` is the
         front of the text the drafter searches (and, under ``penalties``, the source of the prompt flags).  Also the entry point
@@ -1015,30 +732,17 @@ class LlamaGlide(LlamaForCausalLM):
         gamma, max_ngram, min_ngram = _lookup_check(gamma, max_ngram, min_ngram, branches)
         bsz = first_token.size(0)
         dev = first_token.device
-        sampling = _resolve_sampling(sampling, None, use_env=True)
-        penalties = _resolve_penalties(penalties, None, use_env=True)
-        logprobs = _resolve_logprobs(logprobs, None, use_env=True)
-        stop = _resolve_stop(stop, None, use_env=True)
-        ban = _resolve_ban(ban, None, use_env=True)
-        guide = _resolve_guide(guide, None, use_env=True)
+        if rules is None:
+            rules = self._rules(dev, None, self.model.layers[-1].self_attn.shard, sampling=sampling, penalties=penalties,
+                                logprobs=logprobs, stop=stop, ban=ban, guide=guide)
         if branches > 1:
             return self._begin_lookup_tree(first_token, cache_lens, input_len, int(prompt_bound), prompt_ids, gamma, branches,
-                                           max_ngram, min_ngram, max_gen_len, eos_id, sampling, penalties, prompt_state, logprobs,
-                                           first_logprobs, stop, stop_table, ban, ban_table, guide, guide_table)
+                                           max_ngram, min_ngram, max_gen_len, eos_id, rules)
         st = _DecodeState(gamma=gamma, max_ngram=max_ngram, min_ngram=min_ngram, bsz=bsz, P=int(prompt_bound),
-                          max_gen_len=max_gen_len, count=0, num=0, emitted=1, rounds=0, sampling=sampling)
-        st.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if sampling is not None else None
+                          max_gen_len=max_gen_len, count=0, num=0, emitted=1, rounds=0)
         st.prompt_ids = prompt_ids.to(device=dev, dtype=torch.int64)
         if st.prompt_ids.stride(-1) != 1:
             st.prompt_ids = st.prompt_ids.contiguous()
-        self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
-        self._begin_ban(st, ban, dev, ban_table)
-        self._begin_guide(st, guide, bsz, dev, first_token, guide_table)
-        st.chain_mask = None
-        if penalties is not None or st.ban is not None or st.guide is not None:
-            # verification row i follows the draft tokens spec_buffer[:, 1 : i + 1]
-            st.chain_mask = torch.ones((gamma + 1, gamma), dtype=torch.int64, device=dev).tril(-1)
-        self._begin_logprobs(st, logprobs, bsz, max_gen_len + gamma, dev, first_logprobs)
         st.output_ids = first_token.new_zeros((bsz, max_gen_len + gamma))
         st.spec_mask = first_token.new_zeros((bsz, max_gen_len + gamma))
         st.output_ids[:, 0] = first_token
@@ -1054,59 +758,47 @@ class LlamaGlide(LlamaForCausalLM):
         st.hist = torch.zeros((bsz, max_ngram + 1), dtype=torch.int64, device=dev)
         st.last_lookup = SimpleNamespace(hist=st.hist, info=st.info)
         st.eos = self._stop_id(eos_id, "spec")
-        self._begin_stop(st, stop, bsz, dev, stop_table)
-        if st.stop is not None:                              # column 0; a hit ends the loop with its first round
-            self._stop_scan(st, st.cache_lens, st.input_len_i32, 1)
+        rules.bind(st, first_token, prompt_ids, input_len, (st.cache_lens, st.input_len_i32, 1, 0), gamma=gamma)
         st.use_graphs = bool(dev.type == "cuda" and bsz == 1 and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
         P, rows = st.P, gamma + 2                          # (the replayer holds no reference to the state that holds it)
         st.replayer = GraphReplayer(self, lambda bound: (P + bound + rows, P + bound + rows), st.output_ids.size(1), "lookup round")
         return st
 
+    def _chain_verify(self, st, spec_logits=None):
+        """The verification half of a chain-shaped round (``chain_round``, ``_lookup_device``), device work only: the
+        (gamma + 1)-row target pass over ``spec_buffer``, the rules on its rows (row i follows the text and i draft tokens),
+        the arg-max or draw, ``chain_commit`` and the rules' commits.  ``spec_logits``: the draft's logits, for the reference's
+        rejection test at temperature > 0 (:715-736).  Returns state [bsz, 2] = (correct_len, EOS hit | 2 * stop hit)."""
+        gamma, rules, cache_lens, spec_buffer = st.gamma, st.rules, st.cache_lens, st.spec_buffer
+        hidden_states = self.model.forward(spec_buffer, cache_lens=cache_lens, exec_type="decoding").last_hidden_state
+        llm_verify_logits = rules.apply(self.lm_head(hidden_states[:, -gamma - 1:, :]), spec_buffer[:, 1:], rules.chain_mask,
+                                        depth="row")
+        # (sampling: verification row i was rotated to position cache_lens + i, models' forward :571-577)
+        llm_verify_output = rules.tokens(llm_verify_logits,
+                                         cache_lens[:, None] + rules.arange_v if rules.sampling is not None else None)
+        # every verification row's log-probs; the commit keeps a prefix of them, at the columns behind the text as it stands
+        # BEFORE chain_commit advances it
+        pending = rules.pending(llm_verify_logits, llm_verify_output)
+        accept = {}
+        if spec_logits is not None:
+            llm_verify_output, mask = self.ops.chain_accept_stochastic(spec_logits, llm_verify_logits, spec_buffer, llm_verify_output)
+            accept = {"accept_mask": mask}
+        # acceptance by cumulative match, verified ids + bonus token -> output_ids, cache_lens += correct_len, the next
+        # round's start tokens and draft_cache_lens = cache_lens - double_input (:738-770): one launch, one host read
+        state = self.ops.chain_commit(llm_verify_output, spec_buffer, st.output_ids, cache_lens, st.draft_cache_lens,
+                                      st.input_len_i32, st.next_spec_start_token, st.eos, **accept)
+        rules.record(pending, state[:, 0])                   # the correct_len tokens this round wrote, before the host read
+        rules.advance(llm_verify_output, state[:, 0], state)
+        return state
+
     def _lookup_device(self, st):
         """The device work of one lookup round (no host read inside, no host-side parameter): the draft from the text, then
-        the verification half of ``chain_round``, operator for operator.  The drafter's grid is sized from the bound the
-        round's attention launches are sized from (``_set_hints``: the eager round's, or the graph tier's).  Returns state
-        [bsz, 2] = (correct_len, EOS hit | 2 * stop hit)."""
-        gamma = st.gamma
-        output_ids, cache_lens, spec_buffer = st.output_ids, st.cache_lens, st.spec_buffer
-        bound = self.model.layers[-1].self_attn.kv_len_hint or st.P + output_ids.size(1)
-        self.ops.ngram_draft(st.prompt_ids, st.input_len_i32, output_ids, cache_lens, bound, gamma, st.max_ngram, st.min_ngram,
-                             spec_buffer, info=st.info, hist=st.hist)
-        hidden_states = self.model.forward(spec_buffer, cache_lens=cache_lens, exec_type="decoding").last_hidden_state
-        llm_verify_logits = self.lm_head(hidden_states[:, -gamma - 1:, :])
-        if st.penalties is not None:
-            llm_verify_logits = self.ops.penalize_rows(llm_verify_logits, st.token_state, st.penalties, spec_buffer[:, 1:],
-                                                       st.chain_mask, bias=st.bias_table)
-        if st.stop is not None and st.stop.min_tokens > 0:   # row i predicts column cache_lens - input_len + 1 + i
-            llm_verify_logits = self.ops.stop_ban_rows(llm_verify_logits, st.stop.table, base=cache_lens, base_sub=st.input_len_i32,
-                                                       base_add=1, depth="row")
-        if st.ban is not None:                               # row i: columns 0 .. cache_lens - input_len, then i draft tokens
-            llm_verify_logits = self.ops.ban_rows(llm_verify_logits, st.ban.table, output_ids, base=cache_lens,
-                                                  base_sub=st.input_len_i32, base_add=1, extra_ids=spec_buffer[:, 1:],
-                                                  extra_mask=st.chain_mask)
-        if st.guide is not None:                             # row i: the committed state walked along i draft tokens
-            llm_verify_logits = self.ops.guide_rows(llm_verify_logits, st.guide.table, st.guide.state,
-                                                    extra_ids=spec_buffer[:, 1:], extra_mask=st.chain_mask)
-        # (sampling: verification row i was rotated to position cache_lens + i)
-        llm_verify_output = self._target_tokens(llm_verify_logits, st.sampling,
-                                                cache_lens[:, None] + st.arange_v if st.sampling is not None else None)
-        lp_rows = lp_base = None
-        if st.logprobs is not None:
-            lp_rows = self.ops.token_logprobs(llm_verify_logits, llm_verify_output, st.logprobs.temperature, st.logprobs.top_n)
-            lp_base = (cache_lens - st.input_len_i32).to(torch.int32)
-        # acceptance by cumulative match, verified ids + bonus token -> output_ids, cache_lens += correct_len, and the bonus
-        # token -> spec_buffer[:, 0], the next round's start token
-        state = self.ops.chain_commit(llm_verify_output, spec_buffer, output_ids, cache_lens, st.draft_cache_lens, st.input_len_i32,
-                                      st.next_spec_start_token, st.eos)
-        if st.penalties is not None:                         # the correct_len tokens this round wrote, before the host read
-            self.ops.token_state_add(st.token_state, llm_verify_output, num=state[:, 0])
-        if st.guide is not None:                             # ... and the automaton follows them
-            self.ops.guide_advance(st.guide.state, st.guide.table, llm_verify_output, num=state[:, 0])
-        if lp_rows is not None:                              # ... and their log-probs, to the columns chain_commit wrote
-            self.ops.logprob_commit(lp_rows, st.logprobs, lp_base, base_add=1, num=state[:, 0])
-        if st.stop is not None:                              # the stop test on those columns; a hit rides in state[:, 1] (bit 1)
-            self._stop_scan(st, cache_lens, st.input_len_i32, 1, num=state[:, 0], state=state)
-        return state
+        the verification half of ``chain_round``.  The drafter's grid is sized from the bound the round's attention launches
+        are sized from (``_set_hints``: the eager round's, or the graph tier's)."""
+        bound = self.model.layers[-1].self_attn.kv_len_hint or st.P + st.output_ids.size(1)
+        self.ops.ngram_draft(st.prompt_ids, st.input_len_i32, st.output_ids, st.cache_lens, bound, st.gamma, st.max_ngram,
+                             st.min_ngram, st.spec_buffer, info=st.info, hist=st.hist)
+        return self._chain_verify(st)
 
     def lookup_round(self, st) -> bool:
         """One round of ``lookup_generate``: the draft from the text, one (gamma + 1)-row target pass, acceptance by cumulative
@@ -1149,8 +841,7 @@ class LlamaGlide(LlamaForCausalLM):
         return not hit
 
     def _begin_lookup_tree(self, first_token, cache_lens, input_len, P: int, prompt_ids, gamma, branches, max_ngram, min_ngram,
-                           max_gen_len, eos_id, sampling, penalties, prompt_state, logprobs, first_logprobs, stop, stop_table,
-                           ban=None, ban_table=None, guide=None, guide_table=None):
+                           max_gen_len, eos_id, rules):
         """State of the lookup loop with ``branches >= 2``: ``begin_tree_decode``'s without anything that belongs to a draft
         layer -- ``all_spec`` / ``tree_mask`` of the static level-major tree (Fn = 1 + branches * gamma nodes), ``acc_pad``
         [bsz, gamma + 1], ``a``, ``emitted_dev``, int32 ``cache_lens``, R = Fn - 1 + gamma + 1 verification rows -- and the
@@ -1163,16 +854,12 @@ class LlamaGlide(LlamaForCausalLM):
         R = Fn - 1 + gamma + 1
         width = max_gen_len + gamma + 1
         st = _DecodeState(gamma=gamma, branches=branches, max_ngram=max_ngram, min_ngram=min_ngram, Fn=Fn, R=R, P=P, dev=dev,
-                          bsz=bsz, sampling=sampling, max_gen_len=max_gen_len, rounds=0)
+                          bsz=bsz, max_gen_len=max_gen_len, rounds=0)
         st.prompt_ids = prompt_ids.to(device=dev, dtype=torch.int64)
         if st.prompt_ids.stride(-1) != 1:
             st.prompt_ids = st.prompt_ids.contiguous()
         st.input_len = input_len
         st.input_len_i32 = input_len.to(device=dev, dtype=torch.int32).view(bsz).contiguous()
-        self._begin_penalties(st, penalties, bsz, dev, prompt_ids, input_len, first_token, prompt_state)
-        self._begin_logprobs(st, logprobs, bsz, width, dev, first_logprobs)
-        self._begin_ban(st, ban, dev, ban_table)
-        self._begin_guide(st, guide, bsz, dev, first_token, guide_table)
         st.fill = self._tree_output_fill(eos_id)
         st.output_ids = torch.full((bsz, width), st.fill, dtype=torch.int64, device=dev)
         st.spec_mask = torch.zeros((bsz, width), dtype=torch.int64, device=dev)
@@ -1183,7 +870,7 @@ class LlamaGlide(LlamaForCausalLM):
         st.all_spec[:, 0] = first_token
         st.tree_mask = torch.zeros((bsz, Fn, Fn), dtype=torch.int64, device=dev)
         st.tree_mask[:, :, 0] = 1
-        st.logp_sum = torch.zeros((bsz, Fn), dtype=torch.float32, device=dev)   # (tree_commit resets it with the rest)
+        st.history_logp_sum = torch.zeros((bsz, Fn), dtype=torch.float32, device=dev)   # (tree_commit resets it with the rest)
         st.acc_pad = torch.zeros((bsz, gamma + 1), dtype=torch.int64, device=dev)
         st.acc_pad[:, 0] = first_token
         st.acc_ids = st.acc_pad[:, :1]
@@ -1196,17 +883,40 @@ class LlamaGlide(LlamaForCausalLM):
         st.won = torch.zeros((bsz, branches), dtype=torch.int64, device=dev)
         st.last_lookup = SimpleNamespace(hist=st.hist, info=st.info, branches=branches, hist_nb=st.hist_nb, won=st.won)
         st.eos = self._stop_id(eos_id, "tree")
-        self._begin_stop(st, stop, bsz, dev, stop_table)
-        if st.stop is not None:                              # column 0; a hit ends the loop with its first round
-            self._stop_scan(st, st.emitted_dev, fill=st.fill)
+        rules.bind(st, first_token, prompt_ids, input_len, (st.emitted_dev, None, 0, st.fill))
         st.use_graphs = bool(dev.type == "cuda" and bsz == 1 and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
         st.replayer = GraphReplayer(self, lambda bound: (P + bound + R, P + bound + R), width, "lookup tree round")
         return st
 
+    def _tree_accept(self, st, a: int, llm_logits, position_ids, collapse, commit, pred=None):
+        """The accept half of a tree-shaped round (``_round_device``, ``_lookup_tree_device``), device work only, from the
+        target's logits of rows a-1 .. a+Fn-2: the rules (row j follows the committed text, the root included, and the nodes on
+        node j's path -- the trees grow level by level, so increasing column is increasing depth -- and predicts column
+        emitted + depth(j)), the arg-max or draw at the positions RoPE saw, ``tree_collapse(..., *collapse)``,
+        ``tree_commit(..., **commit)`` and the rules' commits.  ``pred``: the tokens, where a ``vocab_parallel`` shard's
+        ``head_select`` took them and no row of logits exists.  Returns (state [bsz, 2] = (acc_num, EOS hit | 2 * stop hit),
+        acc_num, index_mapping)."""
+        ops, rules, all_spec, tree_mask = self.ops, st.rules, st.all_spec, st.tree_mask
+        pending = None
+        if pred is None:
+            llm_logits = rules.apply(llm_logits, all_spec[:, 1:], tree_mask[:, :, 1:], depth="tree", tree_mask=tree_mask)
+            pred = rules.tokens(llm_logits, position_ids[:, a - 1:a + st.Fn - 1] if rules.sampling is not None else None)
+            pending = rules.pending(llm_logits, pred)
+        acc_pad, acc_num_t, _, index_mapping = ops.tree_collapse(all_spec, pred, tree_mask, *collapse, out_acc_ids=st.acc_pad)
+        # the accepted rows' log-probs -> the columns tree_commit is about to write, behind emitted_dev as it stands now
+        rules.record(pending, acc_num_t, index_mapping)
+        # emitted tokens -> output_ids (at the device-side offset), the EOS test on the whole buffer as the reference
+        # does (:1120, G8), the tree state reset and the length bookkeeping (:1104-1117): one launch; its result is the round's
+        # ONE host read for (acc_num, eos flag)
+        state = ops.tree_commit(acc_pad, acc_num_t, st.output_ids, 0, st.eos, tree_mask, all_spec, st.history_logp_sum,
+                                target_lens=st.cache_lens, target_add=a, emitted_dev=st.emitted_dev, **commit)
+        rules.advance(acc_pad, acc_num_t, state)             # the accepted tokens, inside the round (and its graph)
+        return state, acc_num_t, index_mapping
+
     def _lookup_tree_device(self, st, a: int):
         """The device work of one lookup round with ``branches >= 2`` (no host read inside; ``a``, the tokens the last round
-        accepted, is its only host-side parameter): the tree from the text, then the V and A halves of ``_round_device``,
-        operator for operator, without a draft cache to keep.  Returns state [bsz, 2] = (acc_num, EOS hit | 2 * stop hit)."""
+        accepted, is its only host-side parameter): the tree from the text, then the V and A halves of ``_round_device``
+        without a draft cache to keep.  Returns state [bsz, 2] = (acc_num, EOS hit | 2 * stop hit)."""
         Fn, gamma, R, B = st.Fn, st.gamma, st.R, st.branches
         tree_mask, all_spec = st.tree_mask, st.all_spec
         ops = self.ops
@@ -1218,35 +928,9 @@ class LlamaGlide(LlamaForCausalLM):
         veri_spec, position_ids, mask_bits = ops.tree_verify_inputs(acc_ids, a, all_spec, tree_mask, st.cache_lens, R)
         hidden_states = self.model.forward(veri_spec, position_ids=position_ids, cache_lens=st.cache_lens,
                                            exec_type="tree_decoding", tree_mask_bits=mask_bits).last_hidden_state
-        llm_logits = self.lm_head(hidden_states[:, a - 1:a + Fn - 1])
-        if st.penalties is not None:
-            llm_logits = ops.penalize_rows(llm_logits, st.token_state, st.penalties, all_spec[:, 1:], tree_mask[:, :, 1:],
-                                           bias=st.bias_table)
-        if st.stop is not None and st.stop.min_tokens > 0:
-            llm_logits = ops.stop_ban_rows(llm_logits, st.stop.table, base=st.emitted_dev, depth="tree", tree_mask=tree_mask)
-        if st.ban is not None:            # row j: the committed columns, then the nodes on its path (level-major: path order)
-            llm_logits = ops.ban_rows(llm_logits, st.ban.table, st.output_ids, base=st.emitted_dev, extra_ids=all_spec[:, 1:],
-                                      extra_mask=tree_mask[:, :, 1:])
-        if st.guide is not None:          # row j: the committed state walked along the nodes on its path
-            llm_logits = ops.guide_rows(llm_logits, st.guide.table, st.guide.state, extra_ids=all_spec[:, 1:],
-                                        extra_mask=tree_mask[:, :, 1:])
-        all_llm_pred = self._target_tokens(llm_logits, st.sampling,
-                                           position_ids[:, a - 1:a + Fn - 1] if st.sampling is not None else None)
         # ---- A: the deepest branch that verifies; no KV row moves (the next pass feeds the accepted tokens again)
-        acc_pad, acc_num_t, _, index_mapping = ops.tree_collapse(all_spec, all_llm_pred, tree_mask, st.cache_lens,
-                                                                 1 + B * (gamma - 1), gamma + 1, out_acc_ids=st.acc_pad)
-        if st.logprobs is not None:
-            lp = st.logprobs
-            ops.logprob_commit(ops.token_logprobs(llm_logits, all_llm_pred, lp.temperature, lp.top_n), lp, st.emitted_dev,
-                               num=acc_num_t, index_map=index_mapping)
-        state = ops.tree_commit(acc_pad, acc_num_t, st.output_ids, 0, st.eos, tree_mask, all_spec, st.logp_sum,
-                                target_lens=st.cache_lens, target_add=a, emitted_dev=st.emitted_dev)
-        if st.penalties is not None:
-            ops.token_state_add(st.token_state, acc_pad, num=acc_num_t)
-        if st.guide is not None:
-            ops.guide_advance(st.guide.state, st.guide.table, acc_pad, num=acc_num_t)
-        if st.stop is not None:
-            self._stop_scan(st, st.emitted_dev, num=acc_num_t, fill=st.fill, state=state)
+        state, acc_num_t, index_mapping = self._tree_accept(st, a, self.lm_head(hidden_states[:, a - 1:a + Fn - 1]), position_ids,
+                                                            (st.cache_lens, 1 + B * (gamma - 1), gamma + 1), {})
         # the branch of the deepest accepted node (node = 1 + (d-1) * B + j), where a draft token was accepted at all
         n = acc_num_t.view(-1, 1).to(torch.int64)
         last = index_mapping.gather(1, (n - 1).clamp(min=0))
@@ -1284,40 +968,12 @@ class LlamaGlide(LlamaForCausalLM):
                            logprobs=None, stop=None, ban=None, guide=None):                                               # :915-1126
         """``shard`` (``dist.KVShard``, every rank of the group calls with the same arguments): the prompt is prefilled
         and its KV kept sequence-sharded over the ranks (``_sharded_prefill``); decoding then runs replicated with one
-        exchange per attention call.  Returns the same values on every rank.  ``sampling``: the verification pass draws
-        one token per row and the greedy acceptance runs on the draws (not with a vocabulary-parallel shard).  ``penalties``:
-        every verification row is penalised from its own history -- prompt, text so far and the tree path it follows (not with
-        a vocabulary-parallel shard; under a sequence shard every rank keeps the same state).  ``logprobs``: the log-probs of
-        the emitted tokens and their top-n alternatives as ``self.last_logprobs`` (not with a vocabulary-parallel shard; under
-        a sequence shard every rank computes the same values).  ``stop``: stop tokens, stop sequences and ``min_tokens``
-        (``stop.py``), the result as ``self.last_stop``; the stop test reads ``output_ids`` only, so every rank of either shard
-        computes the same result -- ``min_tokens > 0`` alone is refused with a vocabulary-parallel shard.  ``ban``: banned
-        sequences and no-repeat n-grams on every verification row, from the committed text and the row's tree path (``ban.py``;
-        not with a vocabulary-parallel shard; under a sequence shard every rank computes the same rows).  ``guide``: guided
-        decoding on every verification row, from the state behind the committed text walked along the row's tree path
-        (``guide.py``; not with a vocabulary-parallel shard; under a sequence shard every rank keeps the same state)."""
+        exchange per attention call.  Returns the same values on every rank.  The six keywords: ``target_rules.py``, on every
+        verification row; the log-probs are published as ``self.last_logprobs``, the stop result as ``self.last_stop``.  With
+        a ``vocab_parallel`` shard all of them but a ``stop`` without ``min_tokens`` are refused."""
         assert input_ids is not None, "please give the input"
-        sampling = _resolve_sampling(sampling, temperature, use_env=True)
-        pen = _resolve_penalties(penalties, temperature, use_env=True)
-        lpc = _resolve_logprobs(logprobs, temperature, use_env=True)
-        stp = _resolve_stop(stop, temperature, use_env=True)
-        if stp is not None and stp.min_tokens > 0 and shard is not None and shard.vocab_parallel:
-            raise ValueError("stop= with min_tokens > 0 is not available with a vocabulary-parallel shard")
-        stab = stp.table(self.lm_head.out_features, input_ids.device) if stp is not None else None     # (checks the ids: before any prefill)
-        if sampling is not None and shard is not None and shard.vocab_parallel:
-            raise ValueError("sampling= is not available with a vocabulary-parallel shard")
-        if pen is not None and shard is not None and shard.vocab_parallel:
-            raise ValueError("penalties= is not available with a vocabulary-parallel shard")
-        if lpc is not None and shard is not None and shard.vocab_parallel:
-            raise ValueError("logprobs= is not available with a vocabulary-parallel shard")
-        bn = _resolve_ban(ban, temperature, use_env=True)
-        if bn is not None and shard is not None and shard.vocab_parallel:
-            raise ValueError("ban= is not available with a vocabulary-parallel shard")
-        btab = bn.table(self.lm_head.out_features, input_ids.device) if bn is not None else None
-        gd = _resolve_guide(guide, temperature, use_env=True)
-        if gd is not None and shard is not None and shard.vocab_parallel:
-            raise ValueError("guide= is not available with a vocabulary-parallel shard")
-        gtab = gd.table(self.lm_head.out_features, input_ids.device) if gd is not None else None
+        rules = self._rules(input_ids.device, temperature, shard, head_sharded=True, sampling=sampling, penalties=penalties,
+                            logprobs=logprobs, stop=stop, ban=ban, guide=guide)
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
         dev = input_ids.device
@@ -1331,29 +987,24 @@ class LlamaGlide(LlamaForCausalLM):
         for layer in self.model.layers:                    # a model object may be reused with and without a shard
             layer.self_attn.shard = shard
         self.glide.cross_attn.shard = shard
-        pstate = self._token_state(bsz, dev, input_ids, input_len) if pen is not None else None
         if shard is not None:
             if dev.type == "cuda" and not shard.peer_tried:
                 # a mailbox slot holds the record of the widest pass: 128 rows x heads x (128 + 1) floats
                 heads = max(self.config.num_attention_heads, self.glide.config.num_attention_heads)
                 shard.enable_peer_exchange(bsz * 128 * heads * 129, dev)
-            first, first_lp = self._sharded_prefill(input_ids, input_len, position_ids, shard, sampling, pen, pstate, lpc, stp,
-                                                    stab, btab, gd, gtab)
+            first = self._sharded_prefill(input_ids, input_len, position_ids, shard, rules)
         else:
             # prefill LLM (:954-960)
             self._set_hints(P, P)
             hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
-            first, first_lp = self._first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), sampling, input_len, pen,
-                                                pstate, lpc, stp, stab, btab, gd, gtab)
+            first = rules.first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), input_len, input_ids)
             # prefill glide (:968-975)
             hidden_states = self.model.embed_tokens(input_ids)
             position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
             self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
                        cache_lens=lens.clone(), llm_kv_len=lens.clone(), exec_type="prefill")
-        st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature, sampling=sampling,
-                                    penalties=penalties, prompt_ids=input_ids, prompt_state=pstate, logprobs=logprobs,
-                                    first_logprobs=first_lp, stop=stop, stop_table=stab, ban=ban, ban_table=btab, guide=guide,
-                                    guide_table=gtab)
+        st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature, prompt_ids=input_ids,
+                                    rules=rules)
         self.last_logprobs = st.logprobs
         self.last_stop = st.last_stop
         _sync(input_ids)
@@ -1372,11 +1023,10 @@ class LlamaGlide(LlamaForCausalLM):
             shard.raise_if_exchange_failed()
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
-    def _sharded_prefill(self, input_ids, input_len, position_ids, shard, sampling=None, penalties=None, prompt_state=None,
-                         logprobs=None, stop=None, stop_table=None, ban_table=None, guide=None, guide_table=None):
+    def _sharded_prefill(self, input_ids, input_len, position_ids, shard, rules):
         """Sequence-sharded prefill: rank r runs the target model on prompt rows [r*Ls, (r+1)*Ls) only
         (one all-gather of the layer's K/V rows per layer, ``LlamaAttention.sharded_prefill``) and keeps that slice of the
-        KV; the tail rank computes the first token (and, under ``logprobs``, its log-prob rows) and broadcasts it.  The
+        KV; the tail rank computes the first token (``rules.first_token``: under ``logprobs`` its log-prob rows too) and broadcasts it.  The
         draft layer's cache is filled on every rank (its rows depend on the token ids only).  Work per rank: 1/W of the projections / MLP, between 1/W^2 (rank 0)
         and (2W-1)/W^2 (tail) of the attention."""
         bsz, P = input_ids.shape
@@ -1397,58 +1047,37 @@ class LlamaGlide(LlamaForCausalLM):
             shard.prefill_ctx = None
         dev = input_ids.device
         first = torch.zeros((bsz,), dtype=torch.int64, device=dev)
-        first_lp = None
-        if logprobs is not None:
-            first_lp = (torch.zeros((bsz, 1), dtype=torch.float32, device=dev),
-                        torch.zeros((bsz, 1, logprobs.top_n), dtype=torch.float32, device=dev),
-                        torch.zeros((bsz, 1, logprobs.top_n), dtype=torch.int64, device=dev))
+        if rules.top_n is not None:
+            rules.first_logprobs = (torch.zeros((bsz, 1), dtype=torch.float32, device=dev),
+                                    torch.zeros((bsz, 1, rules.top_n), dtype=torch.float32, device=dev),
+                                    torch.zeros((bsz, 1, rules.top_n), dtype=torch.int64, device=dev))
         if shard.is_tail:
-            first, first_lp = self._first_token(self.lm_head(hidden_states[:, hi - lo - 1, :]), sampling, input_len, penalties,
-                                                prompt_state, logprobs, stop, stop_table, ban_table, guide, guide_table)
+            first = rules.first_token(self.lm_head(hidden_states[:, hi - lo - 1, :]), input_len, input_ids)
         shard.broadcast_from_tail(first)
-        for t in first_lp or ():
+        for t in rules.first_logprobs or ():
             if t.numel():
                 shard.broadcast_from_tail(t)
         hidden_states = self.model.embed_tokens(input_ids)
         self.glide.prefill_cache_only(hidden_states, self.model.rotary_emb(hidden_states, position_ids))
-        return first, first_lp
+        return first
 
     def begin_tree_decode(self, first_token, cache_lens, prompt_bound: int, tree_shape=None, max_gen_len=64, eos_id=151645,
-                          temperature=0.0, sampling=None, penalties=None, prompt_ids=None, prompt_state=None, logprobs=None,
-                          first_logprobs=None, stop=None, stop_table=None, ban=None, ban_table=None, guide=None, guide_table=None):
+                          temperature=0.0, sampling=None, penalties=None, prompt_ids=None, logprobs=None, stop=None, ban=None,
+                          guide=None, rules=None):
         """State of the round loop right after the two prefills (``llama_glide.py:927-991``).
         ``first_token`` [bsz] = the target's first generated token, ``cache_lens`` [bsz] int32 = valid
         rows of every KV cache, ``prompt_bound`` = host-side bound of it.  Also the entry point of
-        synthetic-KV benchmarks, which fill the caches themselves instead of prefilling.  ``sampling``: the round is the
-        temperature-0 round with the arg-max of the verification logits replaced by one draw per row (None at temperature 0:
-        the process-wide default LONGSPEC_SAMPLING, else greedy).  ``penalties``: the verification rows are penalised in front
-        of that arg-max or draw, row j from ``st.token_state`` (``prompt_ids[z, :cache_lens[z]]``, None: no prompt flags, and
-        the text so far) plus the tokens on node j's path (None at temperature 0: the process-wide default
-        LONGSPEC_PENALTIES, else none).  ``logprobs``: the rows on the accepted path fill their columns of ``st.logprobs``
-        inside the round and its graph (None at temperature 0: the process-wide default LONGSPEC_LOGPROBS, else none;
-        ``first_logprobs``: the first token's rows, for column 0).  ``stop``: every round tests the columns it wrote against
-        the stops (``stop.py``; None at temperature 0: the process-wide default LONGSPEC_STOP, else none; ``stop_table``: its
-        device table, already built) inside the round and its graph, in front of the one host read; a match ends the loop with
-        that round, the columns of ``output_ids`` / ``spec_mask`` / ``st.logprobs`` behind it go back to their fill and
-        ``st.last_stop`` holds (length, which, match_start).  KV lengths, ``st.token_state`` and the host counters ``count`` /
-        ``num`` / ``emitted`` are not rolled back: a stopped state is final and ``last_stop.length`` is the authority.  ``ban``:
-        verification row j carries -inf where the committed text plus the nodes on node j's path forbid a token (``ban.py``;
-        None at temperature 0: the process-wide default LONGSPEC_BAN, else none; ``ban_table``: its device table, already
-        built), inside the round and its graph; the draft passes stay unbanned.  ``guide``: verification row j carries -inf where
-        the automaton has no transition from ``st.guide.state`` (the state behind the committed text, advanced behind every
-        commit inside the round and its graph) walked along the nodes on node j's path; a row whose path leaves the language
-        keeps its bits and is never accepted (``guide.py``; None at temperature 0: the process-wide default LONGSPEC_GUIDE, else
-        none; ``guide_table``: its device table, already built); the draft passes stay unguided."""
+        synthetic-KV benchmarks, which fill the caches themselves instead of prefilling.  The six keywords:
+        ``target_rules.py`` (``rules``: the ``TargetRules`` the caller has built from them already);
+        ``prompt_ids[z, :cache_lens[z]]`` is the prompt the penalty state starts from (None: no prompt flags).  A round is the
+        temperature-0 round with its Fn verification rows ruled inside the round and its graph: row j follows the committed
+        text plus the nodes on node j's path and predicts column emitted + depth(j); the rows on the accepted path fill their
+        log-prob columns.  A ``stop=`` match ends the loop with that round; the host counters ``count`` / ``num`` /
+        ``emitted`` are not rolled back."""
         dev = first_token.device
-        sampling = _resolve_sampling(sampling, temperature, use_env=True)
-        penalties = _resolve_penalties(penalties, temperature, use_env=True)
-        logprobs = _resolve_logprobs(logprobs, temperature, use_env=True)
-        stop = _resolve_stop(stop, temperature, use_env=True)
-        ban = _resolve_ban(ban, temperature, use_env=True)
-        guide = _resolve_guide(guide, temperature, use_env=True)
-        sh = self.model.layers[-1].self_attn.shard
-        if sampling is not None and sh is not None and sh.vocab_parallel:
-            raise ValueError("sampling= is not available with a vocabulary-parallel shard")
+        if rules is None:
+            rules = self._rules(dev, temperature, self.model.layers[-1].self_attn.shard, head_sharded=True, sampling=sampling,
+                                penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide)
         bsz = first_token.shape[0]
         cand = [4, 16, 16, 16, 16] if tree_shape is None else list(tree_shape)
         acc_n = [1]
@@ -1458,11 +1087,7 @@ class LlamaGlide(LlamaForCausalLM):
         gamma = len(cand)
         R = Fn - 1 + gamma + 1               # verification rows: [a accepted | F-1 tree | pads]
         self._head_of_draft_passes()                    # the draft passes' head and its pack exist before the first warm-up round
-        st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz, sampling=sampling)
-        self._begin_penalties(st, penalties, bsz, dev, prompt_ids, cache_lens, first_token, prompt_state)
-        self._begin_logprobs(st, logprobs, bsz, max_gen_len, dev, first_logprobs)
-        self._begin_ban(st, ban, dev, ban_table)
-        self._begin_guide(st, guide, bsz, dev, first_token, guide_table)
+        st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz)
         st.output_ids = torch.full((bsz, max_gen_len), self._tree_output_fill(eos_id), dtype=torch.int64, device=dev)  # :937 (G8)
         st.spec_mask = torch.zeros((bsz, max_gen_len), dtype=torch.int64, device=dev)
         st.output_ids[:, 0] = first_token
@@ -1480,9 +1105,7 @@ class LlamaGlide(LlamaForCausalLM):
         st.emitted = 1                        # tokens written to output_ids so far (host mirror of emitted_dev)
         st.emitted_dev = torch.ones((bsz,), dtype=torch.int32, device=dev)
         st.fill = self._tree_output_fill(eos_id)
-        self._begin_stop(st, stop, bsz, dev, stop_table)
-        if st.stop is not None:                              # column 0; a hit ends the loop with its first round
-            self._stop_scan(st, st.emitted_dev, fill=st.fill)
+        rules.bind(st, first_token, prompt_ids, cache_lens, (st.emitted_dev, None, 0, st.fill))
         # HIP graphs of the round, one per `a`: on a GPU; under a KV shard only when its exchange is the peer-store one
         # (kernel launches only: dist.PeerExchange) -- callers that bracket kernels with events switch it off per round
         sh = self.model.layers[-1].self_attn.shard
@@ -1582,11 +1205,8 @@ class LlamaGlide(LlamaForCausalLM):
             return
         st.graphs_forced = True
         names = ("cache_lens", "target_cache_lens_for_draft", "draft_cache_lens", "tree_mask", "all_spec", "history_logp_sum",
-                 "acc_pad", "output_ids", "emitted_dev") + (("token_state",) if st.token_state is not None else ()) \
-            + (("stop_state",) if st.stop_state is not None else ())
-        lp_bufs = (st.logprobs.token, st.logprobs.top_ids, st.logprobs.top) if st.logprobs is not None else ()
-        if st.guide is not None:            # the automaton's state is decode state too: a warm-up round advances it
-            lp_bufs += (st.guide.state,)
+                 "acc_pad", "output_ids", "emitted_dev")
+        tensors = [getattr(st, n) for n in names] + st.rules.state_tensors()     # (a warm-up round advances the rules' state too)
         with rp.guard():
             rp.roll_over(st.emitted)
             for a in range(1, st.gamma + 2):
@@ -1594,12 +1214,9 @@ class LlamaGlide(LlamaForCausalLM):
                     continue
                 device_round = partial(self._round_device, st, a)
                 if a not in rp.entries:
-                    snap = {n: getattr(st, n).clone() for n in names}
-                    lp_snap = [t.clone() for t in lp_bufs]
+                    snap = [t.clone() for t in tensors]
                     rp.warm(a, device_round)
-                    for n in names:
-                        getattr(st, n).copy_(snap[n])
-                    for t, saved in zip(lp_bufs, lp_snap):
+                    for t, saved in zip(tensors, snap):
                         t.copy_(saved)
                 rp.capture(a, device_round)
 
@@ -1676,31 +1293,12 @@ class LlamaGlide(LlamaForCausalLM):
         hidden_states = hidden_states[:, a - 1:a + Fn - 1]
         if st.temperature > 0:
             return self.lm_head(hidden_states)         # the stochastic branch continues in tree_round_stochastic
-        if vsh is not None:
-            all_llm_pred = vsh.head_select(self.lm_head, hidden_states, ops, argmax=True).view(bsz, -1)
-        else:
-            # (sampling: rows a-1 .. a+Fn-2 of the pass, at the positions ops.tree_verify_inputs gave RoPE for them)
-            llm_logits = self.lm_head(hidden_states)
-            if st.penalties is not None:
-                # row j follows the committed text (the root included) and the nodes on its path: mask row j, root column aside
-                llm_logits = ops.penalize_rows(llm_logits, st.token_state, st.penalties, all_spec[:, 1:], tree_mask[:, :, 1:],
-                                               bias=st.bias_table)
-            if st.stop is not None and st.stop.min_tokens > 0:
-                # row j predicts column emitted + depth(j): the root the next column, a node its depth further on
-                llm_logits = ops.stop_ban_rows(llm_logits, st.stop.table, base=st.emitted_dev, depth="tree", tree_mask=tree_mask)
-            if st.ban is not None:
-                # row j's text: the emitted columns, then the nodes on its path -- tree_grow appends level by level, so
-                # increasing column is increasing depth
-                llm_logits = ops.ban_rows(llm_logits, st.ban.table, st.output_ids, base=st.emitted_dev, extra_ids=all_spec[:, 1:],
-                                          extra_mask=tree_mask[:, :, 1:])
-            if st.guide is not None:
-                # row j: the state behind the emitted columns walked along the nodes on its path, in the same order
-                llm_logits = ops.guide_rows(llm_logits, st.guide.table, st.guide.state, extra_ids=all_spec[:, 1:],
-                                            extra_mask=tree_mask[:, :, 1:])
-            all_llm_pred = self._target_tokens(llm_logits, st.sampling,
-                                               position_ids[:, a - 1:a + Fn - 1] if st.sampling is not None else None)
+        # under a shard with `vocab_parallel` every rank takes the arg-max over its slice of the lm_head: no row of logits to rule
+        pred = vsh.head_select(self.lm_head, hidden_states, ops, argmax=True).view(bsz, -1) if vsh is not None else None
+        llm_logits = self.lm_head(hidden_states) if vsh is None else None
         # ---- A: accept / reject tree collapse + last-layer KV row move (:1104-1116); the accepted rows start at
-        # cache_lens + a - 1 (:1104), the cache lengths themselves advance in the commit below
+        # cache_lens + a - 1 (:1104), the cache lengths themselves advance in the commit (`cache_lens += a`,
+        # `target_cache_lens_for_draft += acc_num`)
         sh = last_attn.shard
         if sh is None:
             kv_lens, kc, vc = st.cache_lens, last_attn.K_Cache, last_attn.V_Cache
@@ -1708,27 +1306,8 @@ class LlamaGlide(LlamaForCausalLM):
             kv_lens, kc, vc = sh.local_len(st.cache_lens), last_attn.K_Cache, last_attn.V_Cache
         else:
             kv_lens, kc, vc = st.cache_lens, None, None
-        acc_pad, acc_num_t, double_input, index_mapping = ops.tree_collapse(all_spec, all_llm_pred, tree_mask, kv_lens, acc_n[-2],
-                                                                            gamma + 1, kc, vc, cache_len_add=a - 1,
-                                                                            out_acc_ids=st.acc_pad)
-        if st.logprobs is not None:
-            # the accepted rows' log-probs -> the columns tree_commit is about to write, behind emitted_dev as it stands now
-            lp = st.logprobs
-            ops.logprob_commit(ops.token_logprobs(llm_logits, all_llm_pred, lp.temperature, lp.top_n), lp, st.emitted_dev,
-                               num=acc_num_t, index_map=index_mapping)
-        # emitted tokens -> output_ids (at the device-side offset), the EOS test on the whole buffer as the reference
-        # does (:1120, G8), the tree state reset and `cache_lens += a`, `target_cache_lens_for_draft += acc_num`
-        # (:1104-1117): one launch; its result is the round's ONE host read for (acc_num, eos flag)
-        state = ops.tree_commit(acc_pad, acc_num_t, st.output_ids, 0, st.eos, tree_mask, all_spec, history_logp_sum,
-                                target_lens=st.cache_lens, target_add=a, draft_kv_lens=st.target_cache_lens_for_draft,
-                                emitted_dev=st.emitted_dev)
-        if st.penalties is not None:                          # the accepted tokens, inside the round (and its graph)
-            ops.token_state_add(st.token_state, acc_pad, num=acc_num_t)
-        if st.guide is not None:                              # ... and the automaton follows them
-            ops.guide_advance(st.guide.state, st.guide.table, acc_pad, num=acc_num_t)
-        if st.stop is not None:                               # the stop test on the columns tree_commit wrote; a hit rides in
-            self._stop_scan(st, st.emitted_dev, num=acc_num_t, fill=st.fill, state=state)      # state[:, 1] (bit 1)
-        return state
+        return self._tree_accept(st, a, llm_logits, position_ids, (kv_lens, acc_n[-2], gamma + 1, kc, vc, a - 1),
+                                 dict(draft_kv_lens=st.target_cache_lens_for_draft), pred)[0]
 
     def tree_round_stochastic(self, st) -> bool:
         """One round at temperature > 0 (``llama_glide.py:997-1102,1110-1121``).  The draft passes and the verification pass

@@ -25,6 +25,8 @@ from types import SimpleNamespace
 
 import torch
 
+from .keyword import resolve_keyword
+
 LOGPROBS_ENV = "LONGSPEC_LOGPROBS"       # "n=5": the process-wide default of the loops and the begin_*_decode functions
 MAX_TOP_N = 20
 
@@ -69,16 +71,10 @@ def env_logprobs():
 
 def resolve(logprobs, temperature, use_env: bool):
     """The ``Logprobs`` a loop runs with: the argument; else, where `use_env` and no temperature is given, the default."""
-    if logprobs is not None:
-        if not isinstance(logprobs, Logprobs):
-            raise TypeError(f"logprobs must be a longspec_amd.Logprobs or None, got {type(logprobs).__name__}")
-        if temperature is not None and temperature > 0:
-            raise ValueError("logprobs= is not available with temperature > 0, the reference's own T > 0 path; sampled "
-                             "decoding with log-probs is sampling= with logprobs=")
-        return logprobs
-    if use_env and not temperature:
-        return env_logprobs()
-    return None
+    return resolve_keyword(logprobs, Logprobs, "logprobs", env_logprobs,
+                           "is not available with temperature > 0, the reference's own T > 0 path; sampled "
+                           "decoding with log-probs is sampling= with logprobs=",
+                           temperature, use_env)
 
 
 def new_buffers(bsz: int, width: int, top_n: int, device) -> SimpleNamespace:

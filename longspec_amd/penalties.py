@@ -17,6 +17,8 @@ from __future__ import annotations
 import math
 import os
 
+from .keyword import resolve_keyword
+
 PENALTIES_ENV = "LONGSPEC_PENALTIES"     # "rep=1.1,pres=0.5,freq=0.2": the process-wide default of the begin_*_decode functions
 
 
@@ -102,14 +104,8 @@ def env_penalties():
 def resolve(penalties, temperature, use_env: bool):
     """The ``Penalties`` a loop runs with, or None when nothing would change: the argument; else, where `use_env` and no
     temperature is given, the default."""
-    if penalties is not None:
-        if not isinstance(penalties, Penalties):
-            raise TypeError(f"penalties must be a longspec_amd.Penalties or None, got {type(penalties).__name__}")
-        if temperature is not None and temperature > 0:
-            raise ValueError("penalties= is not available with temperature > 0: that is the reference's own T > 0 path, kept "
-                             "token for token; penalised sampling is sampling= with penalties=")
-        return None if penalties.changes_nothing else penalties
-    if use_env and not temperature:
-        p = env_penalties()
-        return None if p is None or p.changes_nothing else p
-    return None
+    p = resolve_keyword(penalties, Penalties, "penalties", env_penalties,
+                        "is not available with temperature > 0: that is the reference's own T > 0 path, kept "
+                        "token for token; penalised sampling is sampling= with penalties=",
+                        temperature, use_env)
+    return None if p is None or p.changes_nothing else p

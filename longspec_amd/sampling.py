@@ -9,6 +9,8 @@ from __future__ import annotations
 import math
 import os
 
+from .keyword import resolve_keyword
+
 SAMPLING_ENV = "LONGSPEC_SAMPLING"       # "t=0.6,k=40,p=0.95,m=0.05,typ=0.9,seed=1": the process-wide default of the begin_*_decode functions
 
 
@@ -79,13 +81,7 @@ def env_sampling():
 
 def resolve(sampling, temperature, use_env: bool):
     """The ``Sampling`` a loop runs with: the argument; else, where `use_env` and no temperature is given, the default."""
-    if sampling is not None:
-        if not isinstance(sampling, Sampling):
-            raise TypeError(f"sampling must be a longspec_amd.Sampling or None, got {type(sampling).__name__}")
-        if temperature is not None and temperature > 0:
-            raise ValueError("sampling= and temperature > 0 are two different decoders: sampling= draws every token from the "
-                             "target's distribution, temperature= is the reference's own T > 0 path; give one of them")
-        return sampling
-    if use_env and not temperature:
-        return env_sampling()
-    return None
+    return resolve_keyword(sampling, Sampling, "sampling", env_sampling,
+                           "and temperature > 0 are two different decoders: sampling= draws every token from the "
+                           "target's distribution, temperature= is the reference's own T > 0 path; give one of them",
+                           temperature, use_env)

@@ -34,6 +34,8 @@ from types import SimpleNamespace
 
 import torch
 
+from .keyword import resolve_keyword
+
 STOP_ENV = "LONGSPEC_STOP"       # "ids=128001+128009,seq=13+13|198+198+198,min=8": the process-wide default
 MAX_IDS = 64
 MAX_SEQS = 16
@@ -158,16 +160,10 @@ def env_stop():
 
 def resolve(stop, temperature, use_env: bool):
     """The ``Stop`` a loop runs with: the argument; else, where `use_env` and no temperature is given, the default."""
-    if stop is not None:
-        if not isinstance(stop, Stop):
-            raise TypeError(f"stop must be a longspec_amd.Stop or None, got {type(stop).__name__}")
-        if temperature is not None and temperature > 0:
-            raise ValueError("stop= is not available with temperature > 0, the reference's own T > 0 path; sampled decoding "
-                             "with stop conditions is sampling= with stop=")
-        return stop
-    if use_env and not temperature:
-        return env_stop()
-    return None
+    return resolve_keyword(stop, Stop, "stop", env_stop,
+                           "is not available with temperature > 0, the reference's own T > 0 path; sampled decoding "
+                           "with stop conditions is sampling= with stop=",
+                           temperature, use_env)
 
 
 def new_state(bsz: int, device) -> torch.Tensor:
