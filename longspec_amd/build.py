@@ -20,7 +20,7 @@ LIB = os.path.join(LIBDIR, "liblongspec_hip.so")
 SOURCES = ["attn.hip", "ban.hip", "gemm.hip", "gemm_w8.hip", "gemm_w4.hip", "guide.hip", "logprob.hip", "lookup.hip", "lookup_tree.hip", "misc.hip", "penalty.hip",
            "sample.hip", "sample_band.hip", "stop.hip", "topk.hip", "tree.hip", "xgmi.hip"]
 HEADERS = [os.path.join(CSRC, "ls_common.h"), os.path.join(CSRC, "skinny_gemm.h"), os.path.join(CSRC, "lookup_text.h"),
-           os.path.join(CSRC, "sample_common.h"),
+           os.path.join(CSRC, "sample_common.h"), os.path.join(CSRC, "rule_rows.h"),
            os.path.join(os.path.dirname(HERE), "include", "longspec_hip.h")]
 # -ffp-contract=off: the reference-order roundings (fp16 product, fp16 sum) must not be fused into FMAs
 # -Wno-inline-asm: the LDS-DMA helper names m0 in its clobber list on purpose.  -Wno-division-by-zero: the HOST pass folds

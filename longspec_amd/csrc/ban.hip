@@ -21,7 +21,7 @@
 //                       or n = 0: the workgroup returns at once.
 // A forbidden id inside [0, vocab) is one plain 16-bit store of the -inf pattern; lanes that hit one address store one value.
 // No scratch, no atomics, no floating-point arithmetic; ids are compared as 64-bit integers.
-#include "ls_common.h"
+#include "rule_rows.h"
 
 namespace {
 
@@ -33,54 +33,25 @@ constexpr int BN_ROW_TILE = 32;         // rows a chunk workgroup tests its posi
 static_assert(BN_WORDS == LS_BAN_TABLE_WORDS, "ban table layout");
 static_assert(BN_HALO >= BN_MAX_N - 1 && BN_CHUNK % BN_THREADS == 0 && BN_ROW_TILE % BN_WAVES == 0, "ban tiling");
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-
 struct BanRowsArgs {
-    unsigned short* logits;  // [b, rows, vocab] 16-bit, strides in elements
-    long sb, sr;
-    int rows, vocab;
-    unsigned short ninf;     // the type's -inf pattern
+    RuleRows rr;
     const int32_t* table;
     const int64_t* out;      // output_ids [b, width], row stride out_sb; null with width 0
     long out_sb;
     int width;
-    const int32_t* base;     // w = (base ? base[z] : 0) - (base_sub ? base_sub[z] : 0) + base_add, clamped to 0..width
-    const int32_t* base_sub;
-    int base_add;
-    const int64_t* extra_ids;   // [b, C], row stride ids_sb
-    const int64_t* extra_mask;  // [b, rows, C], strides mask_sb / mask_sr
-    long ids_sb, mask_sb, mask_sr;
-    int C;
+    RuleColumn col;          // w, clamped to 0..width
+    RowExtras ex;            // C <= BN_MAX_EXTRA
 };
-
-// Row r's selected extras into `path`, in increasing column; returns their number (<= C <= BN_MAX_EXTRA).  Called by whole waves.
-__device__ __forceinline__ int assemble_path(const BanRowsArgs& a, int z, int r, int lane, int64_t* path) {
-    int cnt = 0;
-    if (r < a.rows && a.C > 0) {
-        const int64_t* ids = a.extra_ids + (long)z * a.ids_sb;
-        const int64_t* mask = a.extra_mask + (long)z * a.mask_sb + (long)r * a.mask_sr;
-        for (int c0 = 0; c0 < a.C; c0 += BN_WAVE) {
-            const int c = c0 + lane;
-            const int64_t mk = c < a.C ? mask[c] : 0, id = c < a.C ? ids[c] : 0;      // (two independent loads)
-            const bool sel = mk != 0;
-            const unsigned long long bal = __ballot(sel);
-            const int before = __popcll(bal & ((1ull << lane) - 1ull));
-            if (sel) path[cnt + before] = id;                      // cnt + before < C
-            cnt += __popcll(bal);
-        }
-    }
-    return cnt;
-}
 
 // ctx[i] = t[m - 1 - i] for i < keep (= n - 1 <= 15) of row r < rows, whose text has m = w + d >= keep + 1 tokens: the end of the
 // row's path, and in front of it the end of the committed text.  No barrier and no LDS read: a wave builds one row after the
 // other.  Called by whole waves.
-__device__ __forceinline__ void build_context(const BanRowsArgs& a, int z, int r, int lane, int keep, int64_t tail, int64_t* ctx) {
+__device__ __forceinline__ void build_context(const RowExtras& a, int z, int r, int lane, int keep, int64_t tail, int64_t* ctx) {
     const unsigned long long lt = (1ull << lane) - 1ull;
     int d = 0;
     if (a.C > 0) {
-        const int64_t* ids = a.extra_ids + (long)z * a.ids_sb;
-        const int64_t* mask = a.extra_mask + (long)z * a.mask_sb + (long)r * a.mask_sr;
+        const int64_t* ids = a.ids + (long)z * a.ids_sb;
+        const int64_t* mask = a.mask + (long)z * a.mask_sb + (long)r * a.mask_sr;
         // the first 64 columns stay in registers: one round trip for the trees and chains the loops pass (C <= 79)
         const int64_t mk0 = lane < a.C ? mask[lane] : 0, id0 = lane < a.C ? ids[lane] : 0;
         const unsigned long long bal0 = __ballot(mk0 != 0);
@@ -110,13 +81,14 @@ __global__ __launch_bounds__(BN_THREADS) void ban_rows_kernel(const BanRowsArgs 
     __shared__ int32_t s_table[BN_WORDS];                          // (path workgroups)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int z = blockIdx.y;
-    const int V = a.vocab;
+    const int V = a.rr.vocab, rows = a.rr.rows;
+    const unsigned short ninf = a.rr.ninf;
     const int n = clampi(a.table[1], 0, BN_MAX_N);
-    const long w64 = (a.base ? (long)a.base[z] : 0l) - (a.base_sub ? (long)a.base_sub[z] : 0l) + a.base_add;
+    const long w64 = rule_column(a.col, z);
     const int w = w64 < 0 ? 0 : w64 > a.width ? a.width : (int)w64;
     const int64_t* out = a.out + (long)z * a.out_sb;              // (never read with w = 0)
-    unsigned short* logits = a.logits + (long)z * a.sb;
-    const int path_blocks = (a.rows + BN_WAVES - 1) / BN_WAVES;
+    unsigned short* logits = a.rr.logits + (long)z * a.rr.sb;
+    const int path_blocks = (rows + BN_WAVES - 1) / BN_WAVES;
 
     if ((int)blockIdx.x < path_blocks) {
         // ---- one row per wave: the listed sequences against the end of t, and the positions j >= w of the row's path
@@ -126,12 +98,12 @@ __global__ __launch_bounds__(BN_THREADS) void ban_rows_kernel(const BanRowsArgs 
         int64_t* path = s_path[wave];
         for (int i = tid; i < BN_WORDS; i += BN_THREADS) s_table[i] = a.table[i];
         if (tid < BN_HALO) s_text[tid] = w - BN_HALO + tid >= 0 ? out[w - BN_HALO + tid] : 0;
-        const int d = assemble_path(a, z, r, lane, path);
+        const int d = r < rows ? select_path(a.ex, z, r, lane, path) : 0;         // (r is the wave's: uniform)
         __syncthreads();                                           // (every wave of the workgroup gets here)
-        if (r >= a.rows) return;
+        if (r >= rows) return;
         auto text = [&](int i) -> int64_t { return i < w ? s_text[i - (w - BN_HALO)] : path[i - w]; };      // t[i], m - 16 <= i < m
         const int m = w + d;
-        unsigned short* row = logits + (long)r * a.sr;
+        unsigned short* row = logits + (long)r * a.rr.sr;
         const int n_seqs = clampi(s_table[0], 0, BN_MAX_SEQS);
         for (int q = lane; q < n_seqs; q += BN_WAVE) {
             const int off = clampi(s_table[BN_OFFS + q], 0, BN_MAX_SEQS * BN_MAX_SEQ_LEN);
@@ -141,7 +113,7 @@ __global__ __launch_bounds__(BN_THREADS) void ban_rows_kernel(const BanRowsArgs 
             bool hit = true;
             for (int i = 0; hit && i < len - 1; ++i) hit = text(m - len + 1 + i) == (int64_t)s_table[BN_TOKS + off + i];
             const int id = s_table[BN_TOKS + off + len - 1];
-            if (hit && id >= 0 && id < V) row[id] = a.ninf;
+            if (hit && id >= 0 && id < V) row[id] = ninf;
         }
         if (n >= 1) {
             for (int q = lane; q < d; q += BN_WAVE) {             // position j = w + q of the path; j <= m - 1
@@ -150,24 +122,24 @@ __global__ __launch_bounds__(BN_THREADS) void ban_rows_kernel(const BanRowsArgs 
                 bool hit = true;
                 for (int k = 1; hit && k < n; ++k) hit = text(j - k) == text(m - k);
                 const int64_t id = path[q];
-                if (hit && id >= 0 && id < (int64_t)V) row[id] = a.ninf;
+                if (hit && id >= 0 && id < (int64_t)V) row[id] = ninf;
             }
         }
         return;
     }
 
     // ---- a chunk of the committed text against a tile of rows: positions j in [max(c0, n - 1), min(w, c0 + BN_CHUNK))
-    const int tiles = (a.rows + BN_ROW_TILE - 1) / BN_ROW_TILE;
+    const int tiles = (rows + BN_ROW_TILE - 1) / BN_ROW_TILE;
     const int idx = blockIdx.x - path_blocks;
     const int c0 = (idx / tiles) * BN_CHUNK, t0 = (idx % tiles) * BN_ROW_TILE;
     if (n == 0 || c0 >= w || w < n) return;                       // (uniform; w < n: no position; from here on every m >= n)
-    const int tile_rows = a.rows - t0 < BN_ROW_TILE ? a.rows - t0 : BN_ROW_TILE;
+    const int tile_rows = rows - t0 < BN_ROW_TILE ? rows - t0 : BN_ROW_TILE;
     for (int i = tid; i < BN_HALO + BN_CHUNK; i += BN_THREADS) {
         const int g = c0 - BN_HALO + i;
         s_text[i] = g >= 0 && g < w ? out[g] : 0;
     }
     const int64_t tail = lane < BN_MAX_N - 1 && w - 1 - lane >= 0 ? out[w - 1 - lane] : 0;
-    for (int rt = wave; rt < tile_rows; rt += BN_WAVES) build_context(a, z, t0 + rt, lane, n - 1, tail, s_ctx[rt]);
+    for (int rt = wave; rt < tile_rows; rt += BN_WAVES) build_context(a.ex, z, t0 + rt, lane, n - 1, tail, s_ctx[rt]);
     __syncthreads();
 #pragma unroll
     for (int p = 0; p < BN_CHUNK / BN_THREADS; ++p) {
@@ -178,7 +150,7 @@ __global__ __launch_bounds__(BN_THREADS) void ban_rows_kernel(const BanRowsArgs 
         for (int rt = 0; rt < tile_rows; ++rt) {
             bool hit = true;
             for (int k = 1; hit && k < n; ++k) hit = s_text[BN_HALO + jl - k] == s_ctx[rt][k - 1];
-            if (hit) logits[(long)(t0 + rt) * a.sr + id] = a.ninf;
+            if (hit) logits[(long)(t0 + rt) * a.rr.sr + id] = ninf;
         }
     }
 }
@@ -192,25 +164,15 @@ int ls_ban_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t str
                 const int32_t* base_sub, int base_add, const int64_t* extra_ids, int64_t ids_stride_b, const int64_t* extra_mask,
                 int64_t mask_stride_b, int64_t mask_stride_r, int n_extra, void* stream) {
     const char* what = "ls_ban_rows";
-    if (!logits || !table) LS_FAIL(LS_ERR_INVALID_ARG, "%s: null pointer", what);
-    if (dtype != LS_F16 && dtype != LS_BF16) LS_FAIL(LS_ERR_INVALID_ARG, "%s: dtype", what);
-    if (b < 1 || b > 65535 || rows < 1 || rows > 65535 || vocab < 1 || stride_r < vocab || stride_b < 0)
-        LS_FAIL(LS_ERR_INVALID_ARG, "%s: b=%d rows=%d vocab=%d strides %ld / %ld (row stride >= vocab)", what, b, rows, vocab,
-                (long)stride_b, (long)stride_r);
-    if (reinterpret_cast<uintptr_t>(logits) % 2 != 0) LS_FAIL(LS_ERR_INVALID_ARG, "%s: misaligned logits", what);
+    BanRowsArgs a;
+    if (int rc = rule_rows_check(what, logits, table != nullptr, b, rows, vocab, dtype, stride_b, stride_r, a.rr)) return rc;
     if (table_words != LS_BAN_TABLE_WORDS) LS_FAIL(LS_ERR_INVALID_ARG, "%s: the ban table has %d words, not %d", what, table_words, LS_BAN_TABLE_WORDS);
     if (width < 0 || width > (1 << 23) || (width > 0 && (!output_ids || out_stride_b < width)))
         LS_FAIL(LS_ERR_INVALID_ARG, "%s: width=%d (0..2^23) needs output_ids with a row stride %ld >= width", what, width, (long)out_stride_b);
-    if (n_extra < 0 || n_extra > LS_BAN_MAX_EXTRA) LS_FAIL(LS_ERR_INVALID_ARG, "%s: n_extra=%d outside 0..%d", what, n_extra, LS_BAN_MAX_EXTRA);
-    if (n_extra > 0 && (!extra_ids || !extra_mask || ids_stride_b < 0 || mask_stride_b < 0 || mask_stride_r < 0))
-        LS_FAIL(LS_ERR_INVALID_ARG, "%s: n_extra=%d needs extra_ids and extra_mask with strides >= 0", what, n_extra);
-    BanRowsArgs a;
-    a.logits = static_cast<unsigned short*>(logits); a.sb = (long)stride_b; a.sr = (long)stride_r;
-    a.rows = rows; a.vocab = vocab; a.ninf = dtype == LS_F16 ? 0xfc00 : 0xff80;
+    if (int rc = row_extras_check(what, extra_ids, ids_stride_b, extra_mask, mask_stride_b, mask_stride_r, n_extra, LS_BAN_MAX_EXTRA, a.ex))
+        return rc;
     a.table = table; a.out = width > 0 ? output_ids : nullptr; a.out_sb = width > 0 ? (long)out_stride_b : 0l; a.width = width;
-    a.base = base; a.base_sub = base_sub; a.base_add = base_add;
-    a.extra_ids = extra_ids; a.extra_mask = extra_mask;
-    a.ids_sb = (long)ids_stride_b; a.mask_sb = (long)mask_stride_b; a.mask_sr = (long)mask_stride_r; a.C = n_extra;
+    a.col = RuleColumn{base, base_sub, base_add};
     const long chunks = (width + BN_CHUNK - 1) / BN_CHUNK, tiles = (rows + BN_ROW_TILE - 1) / BN_ROW_TILE;
     const long blocks = (rows + BN_WAVES - 1) / BN_WAVES + chunks * tiles;
     if (blocks > 0x7fffffffl) LS_FAIL(LS_ERR_INVALID_ARG, "%s: rows=%d x width=%d needs %ld workgroups", what, rows, width, blocks);

@@ -10,7 +10,7 @@
 // forbidden and a state outside [-1, S) as -1: nothing read from the table indexes memory unclamped.
 //
 //   guide_rows_kernel     grid (slices of LS_GUIDE_SLICE ids, rows, batch), 256 threads.  Every workgroup redoes its row's walk: wave 0
-//                         assembles the row's ordered path in LDS (ballot + prefix, as ban.hip), the workgroup looks the classes
+//                         assembles the row's ordered path in LDS (select_path, rule_rows.h), the workgroup looks the classes
 //                         of all path tokens up in parallel, a lane per position, and follows the chain through next, the one
 //                         serial part (measured: 1.2-1.6 us of the kernel's 11-13, less than the launch a pre-pass would add).
 //                         A dead row: the workgroup returns.  Then the workgroup packs next[s, :] into C allow bits in LDS (a
@@ -19,7 +19,7 @@
 //                         16-bit stores of the forbidden ones.  The logits are never read.
 //   guide_advance_kernel  one wave per batch row: the classes of the accepted ids in parallel, the chain serially.
 // No scratch, no atomics, no floating-point arithmetic.
-#include "ls_common.h"
+#include "rule_rows.h"
 
 namespace {
 
@@ -68,17 +68,11 @@ __device__ __forceinline__ int follow(const GuideTable& t, int s, const int* cls
 }
 
 struct GuideRowsArgs {
-    unsigned short* logits;  // [b, rows, vocab] 16-bit, strides in elements
-    long sb, sr;
-    int rows, vocab;
-    unsigned short ninf;     // the type's -inf pattern
+    RuleRows rr;
     const int32_t* table;
     int table_words;
     const int32_t* state;    // [b]
-    const int64_t* extra_ids;   // [b, C], row stride ids_sb
-    const int64_t* extra_mask;  // [b, rows, C], strides mask_sb / mask_sr
-    long ids_sb, mask_sb, mask_sr;
-    int n_extra;
+    RowExtras ex;            // C <= GD_MAX_EXTRA
 };
 
 __global__ __launch_bounds__(GD_THREADS) void guide_rows_kernel(const GuideRowsArgs a) {
@@ -90,24 +84,11 @@ __global__ __launch_bounds__(GD_THREADS) void guide_rows_kernel(const GuideRowsA
     const int r = blockIdx.y, z = blockIdx.z;
     const GuideTable t = read_header(a.table, a.table_words);
     if (!t.ok) return;                                             // (uniform)
-    const int V = a.vocab, tv = t.vocab < V ? t.vocab : V;         // ids in [tv, V) have no class: forbidden
+    const int V = a.rr.vocab, tv = t.vocab < V ? t.vocab : V;         // ids in [tv, V) have no class: forbidden
 
     // ---- the row's state: the committed state walked along the row's path
     if (wave == 0) {
-        int d = 0;
-        if (a.n_extra > 0) {                                       // (uniform)
-            const int64_t* ids = a.extra_ids + (long)z * a.ids_sb;
-            const int64_t* mask = a.extra_mask + (long)z * a.mask_sb + (long)r * a.mask_sr;
-            for (int c0 = 0; c0 < a.n_extra; c0 += GD_WAVE) {
-                const int c = c0 + lane;
-                const int64_t mk = c < a.n_extra ? mask[c] : 0, id = c < a.n_extra ? ids[c] : 0;    // (two independent loads)
-                const bool sel = mk != 0;
-                const unsigned long long bal = __ballot(sel);
-                const int before = __popcll(bal & ((1ull << lane) - 1ull));
-                if (sel) s_path[d + before] = id;                  // d + before < n_extra <= GD_MAX_EXTRA
-                d += __popcll(bal);
-            }
-        }
+        const int d = select_path(a.ex, z, r, lane, s_path);
         if (lane == 0) s_depth = d;
     }
     __syncthreads();
@@ -128,9 +109,10 @@ __global__ __launch_bounds__(GD_THREADS) void guide_rows_kernel(const GuideRowsA
     __syncthreads();
 
     // ---- the slice: ids [g * 8, g * 8 + 8) per group
-    unsigned short* row = a.logits + (long)z * a.sb + (long)r * a.sr;
+    unsigned short* row = a.rr.logits + (long)z * a.rr.sb + (long)r * a.rr.sr;
     const bool aligned = (reinterpret_cast<uintptr_t>(row) & 15) == 0;        // then every group of the row is 16-byte aligned
-    const unsigned nn = (unsigned)a.ninf * 0x00010001u;
+    const unsigned short ninf = a.rr.ninf;
+    const unsigned nn = (unsigned)ninf * 0x00010001u;
     const int g0 = blockIdx.x * GD_GROUPS, groups = (V + 7) >> 3, full_cls = tv >> 3;    // groups < full_cls: eight classes to read
 #pragma unroll 4
     for (int p = 0; p < GD_GROUPS / GD_THREADS; ++p) {
@@ -167,7 +149,7 @@ __global__ __launch_bounds__(GD_THREADS) void guide_rows_kernel(const GuideRowsA
         } else {
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                if ((forbid >> i) & 1u) row[v0 + i] = a.ninf;
+                if ((forbid >> i) & 1u) row[v0 + i] = ninf;
         }
     }
 }
@@ -208,24 +190,14 @@ int ls_guide_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t s
                   int table_words, const int32_t* state, const int64_t* extra_ids, int64_t ids_stride_b, const int64_t* extra_mask,
                   int64_t mask_stride_b, int64_t mask_stride_r, int n_extra, void* stream) {
     const char* what = "ls_guide_rows";
-    if (!logits || !table || !state) LS_FAIL(LS_ERR_INVALID_ARG, "%s: null pointer", what);
-    if (dtype != LS_F16 && dtype != LS_BF16) LS_FAIL(LS_ERR_INVALID_ARG, "%s: dtype", what);
-    if (b < 1 || b > 65535 || rows < 1 || rows > 65535 || vocab < 1 || stride_r < vocab || stride_b < 0)
-        LS_FAIL(LS_ERR_INVALID_ARG, "%s: b=%d rows=%d vocab=%d strides %ld / %ld (row stride >= vocab)", what, b, rows, vocab,
-                (long)stride_b, (long)stride_r);
-    if (reinterpret_cast<uintptr_t>(logits) % 2 != 0) LS_FAIL(LS_ERR_INVALID_ARG, "%s: misaligned logits", what);
+    GuideRowsArgs a;
+    if (int rc = rule_rows_check(what, logits, table && state, b, rows, vocab, dtype, stride_b, stride_r, a.rr)) return rc;
     if (table_words < LS_GUIDE_HEADER_WORDS || reinterpret_cast<uintptr_t>(table) % 16 != 0)
         LS_FAIL(LS_ERR_INVALID_ARG, "%s: the guide table has %d words (at least %d) and is 16-byte aligned", what, table_words,
                 LS_GUIDE_HEADER_WORDS);
-    if (n_extra < 0 || n_extra > LS_GUIDE_MAX_EXTRA) LS_FAIL(LS_ERR_INVALID_ARG, "%s: n_extra=%d outside 0..%d", what, n_extra, LS_GUIDE_MAX_EXTRA);
-    if (n_extra > 0 && (!extra_ids || !extra_mask || ids_stride_b < 0 || mask_stride_b < 0 || mask_stride_r < 0))
-        LS_FAIL(LS_ERR_INVALID_ARG, "%s: n_extra=%d needs extra_ids and extra_mask with strides >= 0", what, n_extra);
-    GuideRowsArgs a;
-    a.logits = static_cast<unsigned short*>(logits); a.sb = (long)stride_b; a.sr = (long)stride_r;
-    a.rows = rows; a.vocab = vocab; a.ninf = dtype == LS_F16 ? 0xfc00 : 0xff80;
+    if (int rc = row_extras_check(what, extra_ids, ids_stride_b, extra_mask, mask_stride_b, mask_stride_r, n_extra, LS_GUIDE_MAX_EXTRA, a.ex))
+        return rc;
     a.table = table; a.table_words = table_words; a.state = state;
-    a.extra_ids = extra_ids; a.extra_mask = extra_mask;
-    a.ids_sb = (long)ids_stride_b; a.mask_sb = (long)mask_stride_b; a.mask_sr = (long)mask_stride_r; a.n_extra = n_extra;
     const dim3 grid((unsigned)((vocab + GD_SLICE - 1) / GD_SLICE), rows, b), block(GD_THREADS);
     hipLaunchKernelGGL(guide_rows_kernel, grid, block, 0, static_cast<hipStream_t>(stream), a);
     LS_CHECK_LAUNCH("guide_rows_kernel");

@@ -15,7 +15,7 @@
 //                           LDS (ballot + prefix, no atomics), then every lane streams 4 x 8 columns with 16-byte accesses and
 //                           counts the extras that fall into them
 //   token_state_add_kernel  grid (ids / 256, batch): one integer atomic per id (add 1, or OR bit 31)
-#include "ls_common.h"
+#include "rule_rows.h"
 
 namespace {
 
@@ -27,11 +27,10 @@ struct PenaltyArgs {
     const void* logits;
     void* out;
     const int32_t* state;
-    const int64_t* extra_ids;
-    const int64_t* extra_mask;
     const float* bias;
-    long in_sb, in_sr, out_sb, out_sr, state_sb, ids_sb, mask_sb, mask_sr;
-    int V, C;
+    long in_sb, in_sr, out_sb, out_sr, state_sb;
+    RowExtras ex;            // C <= PN_MAX_EXTRA
+    int V;
     float repetition, presence, frequency;
 };
 
@@ -45,13 +44,14 @@ __global__ __launch_bounds__(PN_THREADS) void penalize_rows_kernel(const Penalty
     const int V = a.V;
     // ---- the row's selected extras, compacted: order is free (only counts matter), the set is not
     int n_extra = 0;
-    if (a.C > 0) {
-        const int64_t* ids = a.extra_ids + (long)z * a.ids_sb;
-        const int64_t* mask = a.extra_mask + (long)z * a.mask_sb + (long)row * a.mask_sr;
-        for (int base = 0; base < a.C; base += PN_THREADS) {              // (uniform trip count: barriers inside)
+    if (a.ex.C > 0) {
+        const int C = a.ex.C;
+        const int64_t* ids = a.ex.ids + (long)z * a.ex.ids_sb;
+        const int64_t* mask = a.ex.mask + (long)z * a.ex.mask_sb + (long)row * a.ex.mask_sr;
+        for (int base = 0; base < C; base += PN_THREADS) {                // (uniform trip count: barriers inside)
             const int c = base + tid;
             int64_t id = -1;
-            if (c < a.C && mask[c] != 0) id = ids[c];
+            if (c < C && mask[c] != 0) id = ids[c];
             const bool sel = id >= 0 && id < (int64_t)V;
             const unsigned long long bal = __ballot(sel);
             const int before = __popcll(bal & ((1ull << lane) - 1ull));
@@ -160,15 +160,14 @@ int ls_penalize_rows(const void* logits, void* out, int b, int rows, int vocab, 
     if (!aligned16(logits) || !aligned16(out) || !aligned16(state) || (bias && !aligned16(bias)))
         LS_FAIL(LS_ERR_INVALID_ARG, "ls_penalize_rows: logits, out, state and bias must be 16-byte aligned");
     if (!(repetition > 0.f)) LS_FAIL(LS_ERR_INVALID_ARG, "ls_penalize_rows: repetition=%g must be > 0", (double)repetition);
-    if (n_extra < 0 || n_extra > PN_MAX_EXTRA)
-        LS_FAIL(LS_ERR_INVALID_ARG, "ls_penalize_rows: n_extra=%d outside 0..%d", n_extra, PN_MAX_EXTRA);
-    if (n_extra > 0 && (!extra_ids || !extra_mask || ids_stride_b < 0 || mask_stride_b < 0 || mask_stride_r < 0))
-        LS_FAIL(LS_ERR_INVALID_ARG, "ls_penalize_rows: n_extra=%d needs extra_ids and extra_mask with strides >= 0", n_extra);
     PenaltyArgs a;
-    a.logits = logits; a.out = out; a.state = state; a.extra_ids = extra_ids; a.extra_mask = extra_mask; a.bias = bias;
+    if (int rc = row_extras_check("ls_penalize_rows", extra_ids, ids_stride_b, extra_mask, mask_stride_b, mask_stride_r, n_extra,
+                                  PN_MAX_EXTRA, a.ex))
+        return rc;
+    a.logits = logits; a.out = out; a.state = state; a.bias = bias;
     a.in_sb = (long)in_stride_b; a.in_sr = (long)in_stride_r; a.out_sb = (long)out_stride_b; a.out_sr = (long)out_stride_r;
-    a.state_sb = (long)state_stride_b; a.ids_sb = (long)ids_stride_b; a.mask_sb = (long)mask_stride_b; a.mask_sr = (long)mask_stride_r;
-    a.V = vocab; a.C = n_extra;
+    a.state_sb = (long)state_stride_b;
+    a.V = vocab;
     a.repetition = repetition; a.presence = presence; a.frequency = frequency;
     const dim3 grid((vocab + PN_CHUNK - 1) / PN_CHUNK, rows, b), block(PN_THREADS);
     hipStream_t s = static_cast<hipStream_t>(stream);

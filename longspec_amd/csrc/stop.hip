@@ -14,7 +14,7 @@
 // ls_stop_ban_rows  one wave per row of 16-bit target logits: where the row predicts a column < min_tokens, the stop ids' entries
 //                   become -inf (16-bit vector stores of the pattern); every other row and element keeps its bits.
 // No scratch, no LDS, no floating-point arithmetic, no atomics: distinct ids are distinct addresses.
-#include "ls_common.h"
+#include "rule_rows.h"
 
 namespace {
 
@@ -24,8 +24,6 @@ constexpr int ST_IDS = 4, ST_OFFS = ST_IDS + ST_MAX_IDS, ST_TOKS = ST_OFFS + ST_
 constexpr int ST_WORDS = ST_TOKS + ST_MAX_SEQS * ST_MAX_SEQ_LEN;
 static_assert(ST_WORDS == LS_STOP_TABLE_WORDS, "stop table layout");
 constexpr int ST_NO_HIT = 0x7fffffff;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll
@@ -52,9 +50,7 @@ struct ScanArgs {
     int64_t* out;            // output_ids [b, width], row stride out_sb
     long out_sb;
     int width;
-    const int32_t* written;  // columns written so far = written[z] - (written_sub ? written_sub[z] : 0) + written_add
-    const int32_t* written_sub;
-    int written_add;
+    RuleColumn written;      // columns written so far (written.base is never null)
     const int64_t* num;      // columns this round wrote = num[z * num_stride], or num_const without the pointer
     long num_stride;
     int num_const;
@@ -74,7 +70,8 @@ struct ScanArgs {
 __global__ __launch_bounds__(ST_WAVE) void stop_scan_kernel(ScanArgs a) {
     const int z = blockIdx.x, lane = threadIdx.x;
     int64_t* out = a.out + (long)z * a.out_sb;
-    const long w64 = (long)a.written[z] - (a.written_sub ? (long)a.written_sub[z] : 0l) + a.written_add;
+    __builtin_assume(a.written.base != nullptr);                   // (ls_stop_scan refuses a null `written`)
+    const long w64 = rule_column(a.written, z);
     const int w = w64 < 0 ? 0 : w64 > a.width ? a.width : (int)w64;
     int32_t* ss = a.stop_state + (long)z * 4;
     int length = ss[0];
@@ -139,14 +136,9 @@ __global__ __launch_bounds__(ST_WAVE) void stop_scan_kernel(ScanArgs a) {
 }
 
 struct BanArgs {
-    unsigned short* logits;  // [b, rows, vocab] 16-bit, strides in elements
-    long sb, sr;
-    int rows, vocab;
-    unsigned short ninf;     // the type's -inf pattern
+    RuleRows rr;
     const int32_t* table;
-    const int32_t* base;     // row r predicts column (base ? base[z] : 0) - (base_sub ? base_sub[z] : 0) + base_add + depth(r)
-    const int32_t* base_sub;
-    int base_add;
+    RuleColumn col;          // row r predicts this column + depth(r)
     int depth_mode;          // 0: depth 0; 1: depth r; 2: the row sum of mask[z, r, 1:mask_cols]
     const int64_t* mask;
     long mask_sb, mask_sr;
@@ -157,7 +149,7 @@ __global__ __launch_bounds__(ST_WAVE) void stop_ban_rows_kernel(BanArgs a) {
     const int r = blockIdx.x, z = blockIdx.y, lane = threadIdx.x;
     const int min_tokens = a.table[2];
     if (min_tokens <= 0) return;
-    long col = (a.base ? (long)a.base[z] : 0l) - (a.base_sub ? (long)a.base_sub[z] : 0l) + a.base_add;
+    long col = rule_column(a.col, z);
     if (col >= min_tokens) return;                                 // the usual case once the minimum is passed: no mask read
     if (a.depth_mode == 1) {
         col += r;
@@ -171,7 +163,7 @@ __global__ __launch_bounds__(ST_WAVE) void stop_ban_rows_kernel(BanArgs a) {
     const int n_ids = clampi(a.table[0], 0, ST_MAX_IDS);
     if (lane < n_ids) {
         const int id = a.table[ST_IDS + lane];
-        if (id >= 0 && id < a.vocab) a.logits[(long)z * a.sb + (long)r * a.sr + id] = a.ninf;
+        if (id >= 0 && id < a.rr.vocab) a.rr.logits[(long)z * a.rr.sb + (long)r * a.rr.sr + id] = a.rr.ninf;
     }
 }
 
@@ -195,7 +187,7 @@ int ls_stop_scan(int64_t* output_ids, int b, int64_t out_stride_b, int width, co
         LS_FAIL(LS_ERR_INVALID_ARG, "%s: lp_n=%d (0..20) and the log-prob buffers do not go together", what, lp_n);
     ScanArgs a;
     a.out = output_ids; a.out_sb = (long)out_stride_b; a.width = width;
-    a.written = written; a.written_sub = written_sub; a.written_add = written_add;
+    a.written = RuleColumn{written, written_sub, written_add};
     a.num = num; a.num_stride = (long)num_stride; a.num_const = num_const;
     a.table = table; a.stop_state = stop_state; a.fill = fill;
     a.round_state = round_state; a.state_sb = (long)state_stride_b;
@@ -211,21 +203,14 @@ int ls_stop_ban_rows(void* logits, int b, int rows, int vocab, int dtype, int64_
                      int table_words, const int32_t* base, const int32_t* base_sub, int base_add, int depth_mode,
                      const int64_t* mask, int64_t mask_stride_b, int64_t mask_stride_r, int mask_cols, void* stream) {
     const char* what = "ls_stop_ban_rows";
-    if (!logits || !table) LS_FAIL(LS_ERR_INVALID_ARG, "%s: null pointer", what);
-    if (dtype != LS_F16 && dtype != LS_BF16) LS_FAIL(LS_ERR_INVALID_ARG, "%s: dtype", what);
-    if (b < 1 || b > 65535 || rows < 1 || rows > 65535 || vocab < 1 || stride_r < vocab || stride_b < 0)
-        LS_FAIL(LS_ERR_INVALID_ARG, "%s: b=%d rows=%d vocab=%d strides %ld / %ld (row stride >= vocab)", what, b, rows, vocab,
-                (long)stride_b, (long)stride_r);
-    if (reinterpret_cast<uintptr_t>(logits) % 2 != 0) LS_FAIL(LS_ERR_INVALID_ARG, "%s: misaligned logits", what);
+    BanArgs a;
+    if (int rc = rule_rows_check(what, logits, table != nullptr, b, rows, vocab, dtype, stride_b, stride_r, a.rr)) return rc;
     if (table_words != LS_STOP_TABLE_WORDS) LS_FAIL(LS_ERR_INVALID_ARG, "%s: the stop table has %d words, not %d", what, table_words, LS_STOP_TABLE_WORDS);
     if (depth_mode < 0 || depth_mode > 2) LS_FAIL(LS_ERR_INVALID_ARG, "%s: depth_mode=%d", what, depth_mode);
     if (depth_mode == 2 && (!mask || mask_cols < 1 || mask_stride_r < mask_cols || mask_stride_b < 0))
         LS_FAIL(LS_ERR_INVALID_ARG, "%s: depth from a mask needs the mask, mask_cols=%d >= 1 and a row stride %ld >= mask_cols", what,
                 mask_cols, (long)mask_stride_r);
-    BanArgs a;
-    a.logits = static_cast<unsigned short*>(logits); a.sb = (long)stride_b; a.sr = (long)stride_r;
-    a.rows = rows; a.vocab = vocab; a.ninf = dtype == LS_F16 ? 0xfc00 : 0xff80;
-    a.table = table; a.base = base; a.base_sub = base_sub; a.base_add = base_add;
+    a.table = table; a.col = RuleColumn{base, base_sub, base_add};
     a.depth_mode = depth_mode; a.mask = mask; a.mask_sb = (long)mask_stride_b; a.mask_sr = (long)mask_stride_r; a.mask_cols = mask_cols;
     hipLaunchKernelGGL(stop_ban_rows_kernel, dim3(rows, b), dim3(ST_WAVE), 0, static_cast<hipStream_t>(stream), a);
     LS_CHECK_LAUNCH("stop_ban_rows_kernel");

@@ -307,6 +307,105 @@ def pack_gate_up4(gate_weight, up_weight) -> PackedWeight4:
     return PackedWeight4(out, N, K, pair=True)
 
 
+# ---- what the wrappers of the logit-rule operators share.  Plain functions of tensor metadata: none touches the device or the
+# library, and ``who`` is the operator's name in the messages (csrc/rule_rows.h is the same conventions behind the C ABI).
+
+def _rows16(x: torch.Tensor, unit_batch_free: bool = False) -> torch.Tensor:
+    """``x`` [rows, V] or [b, R, V] as the kernels load it, 16 bytes at a time -- unit column stride, row strides multiples of 8
+    elements, the first element 16-byte aligned -- or a contiguous copy.  ``unit_batch_free``: a batch of 1 may have any batch
+    stride (``logprob_topk`` launches per batch row)."""
+    lead = x.stride()[1 if unit_batch_free and x.shape[0] == 1 else 0:-1]
+    if x.stride(-1) != 1 or any(s % 8 != 0 for s in lead) or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    return x
+
+
+def _rule_rows(logits: torch.Tensor, who: str):
+    """Logits an operator rewrites IN PLACE: 16-bit [b, V] or [b, R, V] with unit column stride and rows that do not overlap ->
+    (the [b, R, V] view, b, R, V).  The row stride to pass is ``max(x.stride(1), V)`` (a single row may have any)."""
+    if logits.dim() not in (2, 3) or logits.dtype not in _DT or logits.stride(-1) != 1:
+        raise TypeError(f"{who}: logits must be fp16 / bf16 [b, V] or [b, R, V] with unit column stride")
+    x = logits if logits.dim() == 3 else logits.unsqueeze(1)
+    b, R, V = x.shape
+    if (R > 1 and x.stride(1) < V) or (b > 1 and x.stride(0) < V):
+        raise ValueError(f"{who}: overlapping rows")
+    return x, b, R, V
+
+
+def _extras(extra_ids, extra_mask, b: int, R: int, who: str, limit: Optional[int] = None):
+    """A row's extras, ``extra_ids`` int64 [b, C] selected by ``extra_mask`` int64 [b, R, C] or [R, C] (one mask for the whole
+    batch: batch stride 0) -> (ids_p, ids_sb, mask_p, mask_sb, mask_sr, C); no ids or C = 0: no extras.  ``limit``: the
+    operator's column limit; an operator that has one also refuses a mask without ids."""
+    if extra_ids is None or extra_ids.shape[-1] == 0:
+        if limit is not None and extra_mask is not None and extra_ids is None:
+            raise ValueError(f"{who}: extra_mask needs extra_ids")
+        return None, 0, None, 0, 0, 0
+    if extra_mask is None:
+        raise ValueError(f"{who}: extra_ids needs extra_mask")
+    C = extra_ids.shape[-1]
+    if limit is not None and C > limit:
+        raise ValueError(f"{who}: {C} extra columns, at most {limit}")
+    if extra_ids.dtype != torch.int64 or extra_ids.dim() != 2 or extra_ids.shape[0] != b or extra_ids.stride(1) != 1:
+        raise TypeError(f"{who}: extra_ids must be int64 [b, C] with contiguous rows")
+    if extra_mask.dtype != torch.int64 or extra_mask.dim() not in (2, 3) or extra_mask.stride(-1) != 1 \
+            or tuple(extra_mask.shape[-2:]) != (R, C) or (extra_mask.dim() == 3 and extra_mask.shape[0] != b):
+        raise TypeError(f"{who}: extra_mask must be int64 [b, R, C] or [R, C] with unit column stride")
+    return (extra_ids.data_ptr(), extra_ids.stride(0), extra_mask.data_ptr(), extra_mask.stride(0) if extra_mask.dim() == 3 else 0,
+            extra_mask.stride(-2), C)
+
+
+def _num(num, b: int, who: str):
+    """``num`` int64 [b] with any stride, or None -> (num_p, num_s)."""
+    if num is None:
+        return None, 0
+    if num.dtype != torch.int64 or num.numel() != b or num.dim() != 1:
+        raise TypeError(f"{who}: num must be int64 [b]")
+    return num.data_ptr(), num.stride(0)
+
+
+def _id_rows(ids: torch.Tensor, b: int, who: str, most: Optional[int] = None) -> torch.Tensor:
+    """``ids`` int64 [b, n] (or flat, b * n) with unit column stride, copied when it has another; ``most``: 1 <= n <= most."""
+    if ids.dim() == 1:
+        ids = ids.view(b, -1)
+    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] != b:
+        raise TypeError(f"{who}: ids must be int64 [b, n]")
+    if most is not None and not (1 <= ids.shape[1] <= most):
+        raise ValueError(f"{who}: {ids.shape[1]} ids per row, 1..{most}")
+    if ids.shape[1] > 1 and ids.stride(1) != 1:
+        ids = ids.contiguous()
+    return ids
+
+
+def _lp_buffers(triple, b: int, cols: int, n: int, who: str, names) -> None:
+    """The three dense log-prob buffers of ``cols`` rows or columns: fp32 [b, cols], fp32 [b, cols, n], int64 [b, cols, n]."""
+    for t, shape, dt, name in zip(triple, ((b, cols), (b, cols, n), (b, cols, n)), (torch.float32, torch.float32, torch.int64), names):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise TypeError(f"{who}: {name} must be a contiguous {dt} tensor of shape {shape}")
+
+
+def _ngram_buffers(prompt_ids, output_ids, len_bound, info, info_tail, hists, who: str):
+    """What the two n-gram drafters share: the text buffers (int64 [b, columns], unit column stride, rows apart), the host-side
+    ``len_bound``, ``info`` int32 [b, *info_tail] (allocated when None) and the optional histograms ``hists`` = ((tensor, name,
+    columns), ...), int64 [b, columns] -> (b, info)."""
+    for t, name in ((prompt_ids, "prompt_ids"), (output_ids, "output_ids")):
+        if t.dtype != torch.int64 or t.dim() != 2 or t.stride(1) != 1:
+            raise TypeError(f"{who}: {name} must be int64 [b, columns] with contiguous rows")
+    b = output_ids.shape[0]
+    if prompt_ids.shape[0] != b or (b > 1 and (prompt_ids.stride(0) < prompt_ids.shape[1] or output_ids.stride(0) < output_ids.shape[1])):
+        raise ValueError(f"{who}: prompt_ids and output_ids must have one row per batch row, rows apart")
+    if int(len_bound) < 1:
+        raise ValueError(f"{who}: len_bound={len_bound}")
+    shape = (b,) + tuple(info_tail)
+    if info is None:
+        info = torch.empty(shape, dtype=torch.int32, device=output_ids.device)
+    elif info.dtype != torch.int32 or tuple(info.shape) != shape or not info.is_contiguous():
+        raise TypeError(f"{who}: info must be a contiguous int32 [{', '.join(map(str, shape))}] tensor")
+    for t, name, cols in hists:
+        if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != (b, cols) or not t.is_contiguous()):
+            raise TypeError(f"{who}: {name} must be a contiguous int64 [{b}, {cols}] tensor")
+    return b, info
+
+
 def logprob_topk(logits: torch.Tensor, history: Optional[torch.Tensor], k: int,
                  logp_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(logits.float().log_softmax(-1) + history[..., None]).view(bsz, -1).topk(k)`` (llama_glide.py:1019-1020,
@@ -318,9 +417,7 @@ def logprob_topk(logits: torch.Tensor, history: Optional[torch.Tensor], k: int,
     _dev(logits, history, logp_out)
     if logits.dim() == 2:
         logits = logits.unsqueeze(1)
-    if (logits.stride(-1) != 1 or logits.stride(1) % 8 != 0 or (logits.shape[0] > 1 and logits.stride(0) % 8 != 0)
-            or logits.data_ptr() % 16 != 0):                           # the kernel loads 16 bytes at a time
-        logits = logits.contiguous()
+    logits = _rows16(logits, unit_batch_free=True)
     b, R, V = logits.shape
     if logp_out is not None and (logp_out.dtype != torch.float32 or tuple(logp_out.shape) != (b, R, V) or logp_out.stride(-1) != 1):
         raise TypeError("logprob_topk: logp_out must be fp32 [bsz, rows, V] with a contiguous last dimension")
@@ -356,9 +453,7 @@ def argmax_rows(logits: torch.Tensor) -> torch.Tensor:
     _dev(logits)
     shape = logits.shape[:-1]
     V = logits.shape[-1]
-    x = logits.reshape(-1, V)
-    if x.stride(-1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
-        x = x.contiguous()
+    x = _rows16(logits.reshape(-1, V))
     out = torch.empty((x.shape[0],), dtype=torch.int64, device=logits.device)
     lib = _C.load()
     need = lib.ls_topk_workspace_bytes(x.shape[0], V, 1)
@@ -383,9 +478,7 @@ def sample_rows(logits: torch.Tensor, positions: torch.Tensor, sampling, streams
     min_p, typical_p = float(getattr(sampling, "min_p", 0.0)), float(getattr(sampling, "typical_p", 1.0))
     shape = logits.shape[:-1]
     V = logits.shape[-1]
-    x = logits.reshape(-1, V)
-    if x.stride(-1) != 1 or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
-        x = x.contiguous()
+    x = _rows16(logits.reshape(-1, V))
     n = x.shape[0]
     pos = positions.reshape(-1).to(torch.int64).contiguous()
     if pos.numel() != n:
@@ -445,25 +538,10 @@ def penalize_rows(logits: torch.Tensor, state: torch.Tensor, penalties, extra_id
         raise ValueError("penalize_rows: logits [b, V] or [b, R, V]")
     x = logits if logits.dim() == 3 else logits.unsqueeze(1)
     b, R = x.shape[0], x.shape[1]
-    if x.stride(2) != 1 or x.stride(0) % 8 != 0 or x.stride(1) % 8 != 0 or x.data_ptr() % 16 != 0:
-        x = x.contiguous()
+    x = _rows16(x)
     if state.dtype != torch.int32 or tuple(state.shape) != (b, V) or state.stride(1) != 1:
         raise TypeError(f"penalize_rows: state must be int32 [{b}, {V}] with contiguous rows")
-    C = 0
-    ids_p = mask_p = None
-    ids_sb = mask_sb = mask_sr = 0
-    if extra_ids is not None and extra_ids.shape[-1] > 0:
-        if extra_mask is None:
-            raise ValueError("penalize_rows: extra_ids needs extra_mask")
-        C = extra_ids.shape[-1]
-        if extra_ids.dtype != torch.int64 or extra_ids.dim() != 2 or extra_ids.shape[0] != b or extra_ids.stride(1) != 1:
-            raise TypeError("penalize_rows: extra_ids must be int64 [b, C] with contiguous rows")
-        if extra_mask.dtype != torch.int64 or extra_mask.stride(-1) != 1 or tuple(extra_mask.shape[-2:]) != (R, C) \
-                or (extra_mask.dim() == 3 and extra_mask.shape[0] != b) or extra_mask.dim() not in (2, 3):
-            raise TypeError("penalize_rows: extra_mask must be int64 [b, R, C] or [R, C] with unit column stride")
-        ids_p, ids_sb = extra_ids.data_ptr(), extra_ids.stride(0)
-        mask_p, mask_sr = extra_mask.data_ptr(), extra_mask.stride(-2)
-        mask_sb = extra_mask.stride(0) if extra_mask.dim() == 3 else 0
+    ids_p, ids_sb, mask_p, mask_sb, mask_sr, C = _extras(extra_ids, extra_mask, b, R, "penalize_rows")
     out = torch.empty((b, R, V), dtype=x.dtype, device=x.device)
     if bias is None:
         bias = penalties.bias_table(V, x.device)
@@ -484,17 +562,8 @@ def token_state_add(state: torch.Tensor, ids: torch.Tensor, num: Optional[torch.
     if state.dtype != torch.int32 or state.dim() != 2 or state.stride(1) != 1:
         raise TypeError("token_state_add: state must be int32 [b, V] with contiguous rows")
     b, V = state.shape
-    if ids.dim() == 1:
-        ids = ids.view(b, -1)
-    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] != b:
-        raise TypeError("token_state_add: ids must be int64 [b, n]")
-    if ids.shape[1] > 1 and ids.stride(1) != 1:
-        ids = ids.contiguous()
-    num_p, num_s = None, 0
-    if num is not None:
-        if num.dtype != torch.int64 or num.numel() != b or num.dim() != 1:
-            raise TypeError("token_state_add: num must be int64 [b]")
-        num_p, num_s = num.data_ptr(), num.stride(0)
+    ids = _id_rows(ids, b, "token_state_add")
+    num_p, num_s = _num(num, b, "token_state_add")
     _C.check(_C.load().ls_token_state_add(state.data_ptr(), b, V, state.stride(0), ids.data_ptr(), ids.shape[1], ids.stride(0),
                                           num_p, num_s, 1 if prompt else 0, _stream()), "ls_token_state_add")
 
@@ -514,8 +583,7 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, temperature: float =
         raise ValueError("token_logprobs: logits [b, V] or [b, R, V]")
     x = logits if logits.dim() == 3 else logits.unsqueeze(1)
     b, R, V = x.shape
-    if x.stride(2) != 1 or x.stride(0) % 8 != 0 or x.stride(1) % 8 != 0 or x.data_ptr() % 16 != 0:
-        x = x.contiguous()
+    x = _rows16(x)
     if ids.dtype != torch.int64 or ids.numel() != b * R or ids.shape[0] != b:
         raise TypeError(f"token_logprobs: ids must be int64 [{b}, {R}]")
     ids = ids.view(b, R)
@@ -548,11 +616,8 @@ def logprob_commit(rows, out, base: torch.Tensor, base_add: int = 0, num: Option
     b, R = row_lp.shape
     n = top_val.shape[2]
     W = out.token.shape[1]
-    for t, shape, dt, name in ((row_lp, (b, R), torch.float32, "row_lp"), (top_val, (b, R, n), torch.float32, "top_val"),
-                               (top_idx, (b, R, n), torch.int64, "top_idx"), (out.token, (b, W), torch.float32, "out.token"),
-                               (out.top, (b, W, n), torch.float32, "out.top"), (out.top_ids, (b, W, n), torch.int64, "out.top_ids")):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise TypeError(f"logprob_commit: {name} must be a contiguous {dt} tensor of shape {shape}")
+    _lp_buffers(rows, b, R, n, "logprob_commit", ("row_lp", "top_val", "top_idx"))
+    _lp_buffers((out.token, out.top, out.top_ids), b, W, n, "logprob_commit", ("out.token", "out.top", "out.top_ids"))
     if base.dtype != torch.int32 or base.numel() != b or not base.is_contiguous():
         raise TypeError("logprob_commit: base must be a contiguous int32 [b] tensor")
     J, map_p = R, None
@@ -560,11 +625,7 @@ def logprob_commit(rows, out, base: torch.Tensor, base_add: int = 0, num: Option
         if index_map.dtype != torch.int64 or index_map.dim() != 2 or index_map.shape[0] != b or not index_map.is_contiguous():
             raise TypeError("logprob_commit: index_map must be a contiguous int64 [b, J] tensor")
         J, map_p = index_map.shape[1], index_map.data_ptr()
-    num_p, num_s = None, 0
-    if num is not None:
-        if num.dtype != torch.int64 or num.numel() != b or num.dim() != 1:
-            raise TypeError("logprob_commit: num must be int64 [b]")
-        num_p, num_s = num.data_ptr(), num.stride(0)
+    num_p, num_s = _num(num, b, "logprob_commit")
     ptr = lambda t: t.data_ptr() if n else None
     _C.check(_C.load().ls_logprob_commit(row_lp.data_ptr(), ptr(top_val), ptr(top_idx), b, R, n, map_p, J, num_p, num_s,
                                          base.data_ptr(), base_add, out.token.data_ptr(), ptr(out.top), ptr(out.top_ids), W,
@@ -600,12 +661,8 @@ def stop_scan(output_ids: torch.Tensor, table: torch.Tensor, stop_state: torch.T
     tab_p = _stop_table(table, "stop_scan")
     if stop_state.dtype != torch.int32 or tuple(stop_state.shape) != (b, 4) or not stop_state.is_contiguous():
         raise TypeError(f"stop_scan: stop_state must be a contiguous int32 [{b}, 4] tensor")
-    num_p, num_s = None, 0
-    if num is not None:
-        if num.dtype != torch.int64 or num.numel() != b or num.dim() != 1:
-            raise TypeError("stop_scan: num must be int64 [b]")
-        num_p, num_s = num.data_ptr(), num.stride(0)
-    elif num_const < 0:
+    num_p, num_s = _num(num, b, "stop_scan")
+    if num is None and num_const < 0:
         raise ValueError(f"stop_scan: num_const={num_const}")
     state_p, state_s = None, 0
     if state is not None:
@@ -620,10 +677,7 @@ def stop_scan(output_ids: torch.Tensor, table: torch.Tensor, stop_state: torch.T
     n, lp_p = 0, (None, None, None)
     if logprobs is not None:
         n = logprobs.top.shape[2]
-        for t, shape, dt, name in ((logprobs.token, (b, W), torch.float32, "token"), (logprobs.top, (b, W, n), torch.float32, "top"),
-                                   (logprobs.top_ids, (b, W, n), torch.int64, "top_ids")):
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise TypeError(f"stop_scan: logprobs.{name} must be a contiguous {dt} tensor of shape {shape}")
+        _lp_buffers(lp, b, W, n, "stop_scan", ("logprobs.token", "logprobs.top", "logprobs.top_ids"))
         lp_p = (logprobs.token.data_ptr(), logprobs.top.data_ptr() if n else None, logprobs.top_ids.data_ptr() if n else None)
     _C.check(_C.load().ls_stop_scan(output_ids.data_ptr(), b, output_ids.stride(0), W, _len_i32(written, b, "written"),
                                     _len_i32(written_sub, b, "written_sub"), int(written_add), num_p, num_s, int(num_const),
@@ -640,12 +694,7 @@ def stop_ban_rows(logits: torch.Tensor, table: torch.Tensor, base: Optional[torc
     (int64 [b, R, C]).  Where that column is below the table's ``min_tokens``, the entries of its token ids become -inf; every
     other element keeps its bits.  Returns ``logits``."""
     _dev(logits, table, base, base_sub, tree_mask)
-    if logits.dim() not in (2, 3) or logits.dtype not in (torch.float16, torch.bfloat16) or logits.stride(-1) != 1:
-        raise TypeError("stop_ban_rows: logits must be fp16 / bf16 [b, V] or [b, R, V] with unit column stride")
-    x = logits if logits.dim() == 3 else logits.unsqueeze(1)
-    b, R, V = x.shape
-    if (R > 1 and x.stride(1) < V) or (b > 1 and x.stride(0) < V):
-        raise ValueError("stop_ban_rows: overlapping rows")
+    x, b, R, V = _rule_rows(logits, "stop_ban_rows")
     tab_p = _stop_table(table, "stop_ban_rows")
     if depth not in (None, "row", "tree"):
         raise ValueError(f"stop_ban_rows: depth={depth!r} (None, 'row' or 'tree')")
@@ -679,12 +728,7 @@ def ban_rows(logits: torch.Tensor, table: torch.Tensor, output_ids: Optional[tor
     n-gram the text already holds, become -inf; every other element keeps its bits.  The grid is sized from W and C: nothing is
     read back.  Returns ``logits``."""
     _dev(logits, table, output_ids, base, base_sub, extra_ids, extra_mask)
-    if logits.dim() not in (2, 3) or logits.dtype not in (torch.float16, torch.bfloat16) or logits.stride(-1) != 1:
-        raise TypeError("ban_rows: logits must be fp16 / bf16 [b, V] or [b, R, V] with unit column stride")
-    x = logits if logits.dim() == 3 else logits.unsqueeze(1)
-    b, R, V = x.shape
-    if (R > 1 and x.stride(1) < V) or (b > 1 and x.stride(0) < V):
-        raise ValueError("ban_rows: overlapping rows")
+    x, b, R, V = _rule_rows(logits, "ban_rows")
     if table.dtype != torch.int32 or table.dim() != 1 or table.numel() != BAN_TABLE_WORDS or not table.is_contiguous():
         raise TypeError(f"ban_rows: table must be a contiguous int32 [{BAN_TABLE_WORDS}] tensor (Ban.table)")
     out_p, out_sb, W = None, 0, 0
@@ -695,25 +739,7 @@ def ban_rows(logits: torch.Tensor, table: torch.Tensor, output_ids: Optional[tor
         if b > 1 and output_ids.stride(0) < W:
             raise ValueError("ban_rows: output_ids rows must be at least W elements apart")
         out_p, out_sb = (output_ids.data_ptr(), max(output_ids.stride(0), W)) if W else (None, 0)
-    C = 0
-    ids_p = mask_p = None
-    ids_sb = mask_sb = mask_sr = 0
-    if extra_ids is not None and extra_ids.shape[-1] > 0:
-        if extra_mask is None:
-            raise ValueError("ban_rows: extra_ids needs extra_mask")
-        C = extra_ids.shape[-1]
-        if C > BAN_MAX_EXTRA:
-            raise ValueError(f"ban_rows: {C} extra columns, at most {BAN_MAX_EXTRA}")
-        if extra_ids.dtype != torch.int64 or extra_ids.dim() != 2 or extra_ids.shape[0] != b or extra_ids.stride(1) != 1:
-            raise TypeError("ban_rows: extra_ids must be int64 [b, C] with contiguous rows")
-        if extra_mask.dtype != torch.int64 or extra_mask.dim() not in (2, 3) or extra_mask.stride(-1) != 1 \
-                or tuple(extra_mask.shape[-2:]) != (R, C) or (extra_mask.dim() == 3 and extra_mask.shape[0] != b):
-            raise TypeError("ban_rows: extra_mask must be int64 [b, R, C] or [R, C] with unit column stride")
-        ids_p, ids_sb = extra_ids.data_ptr(), extra_ids.stride(0)
-        mask_p, mask_sr = extra_mask.data_ptr(), extra_mask.stride(-2)
-        mask_sb = extra_mask.stride(0) if extra_mask.dim() == 3 else 0
-    elif extra_mask is not None and extra_ids is None:
-        raise ValueError("ban_rows: extra_mask needs extra_ids")
+    ids_p, ids_sb, mask_p, mask_sb, mask_sr, C = _extras(extra_ids, extra_mask, b, R, "ban_rows", BAN_MAX_EXTRA)
     _C.check(_C.load().ls_ban_rows(x.data_ptr(), b, R, V, _dtype(x), x.stride(0), max(x.stride(1), V), table.data_ptr(),
                                    BAN_TABLE_WORDS, out_p, out_sb, W, _len_i32(base, b, "base"), _len_i32(base_sub, b, "base_sub"),
                                    int(base_add), ids_p, ids_sb, mask_p, mask_sb, mask_sr, C, _stream()), "ls_ban_rows")
@@ -742,34 +768,11 @@ def guide_rows(logits: torch.Tensor, table: torch.Tensor, state: torch.Tensor, e
     (state -1) keeps its bits; in a live one every token without a transition in ``table`` (``Guide.table``) becomes -inf and
     every other element keeps its bits.  The grid is sized from V: nothing is read back.  Returns ``logits``."""
     _dev(logits, table, state, extra_ids, extra_mask)
-    if logits.dim() not in (2, 3) or logits.dtype not in (torch.float16, torch.bfloat16) or logits.stride(-1) != 1:
-        raise TypeError("guide_rows: logits must be fp16 / bf16 [b, V] or [b, R, V] with unit column stride")
-    x = logits if logits.dim() == 3 else logits.unsqueeze(1)
-    b, R, V = x.shape
-    if (R > 1 and x.stride(1) < V) or (b > 1 and x.stride(0) < V):
-        raise ValueError("guide_rows: overlapping rows")
+    x, b, R, V = _rule_rows(logits, "guide_rows")
     tab_p, tab_n = _guide_table(table, "guide_rows")
     if state.dtype != torch.int32 or tuple(state.shape) != (b,) or not state.is_contiguous():
         raise TypeError(f"guide_rows: state must be a contiguous int32 [{b}] tensor")
-    C = 0
-    ids_p = mask_p = None
-    ids_sb = mask_sb = mask_sr = 0
-    if extra_ids is not None and extra_ids.shape[-1] > 0:
-        if extra_mask is None:
-            raise ValueError("guide_rows: extra_ids needs extra_mask")
-        C = extra_ids.shape[-1]
-        if C > GUIDE_MAX_EXTRA:
-            raise ValueError(f"guide_rows: {C} extra columns, at most {GUIDE_MAX_EXTRA}")
-        if extra_ids.dtype != torch.int64 or extra_ids.dim() != 2 or extra_ids.shape[0] != b or extra_ids.stride(1) != 1:
-            raise TypeError("guide_rows: extra_ids must be int64 [b, C] with contiguous rows")
-        if extra_mask.dtype != torch.int64 or extra_mask.dim() not in (2, 3) or extra_mask.stride(-1) != 1 \
-                or tuple(extra_mask.shape[-2:]) != (R, C) or (extra_mask.dim() == 3 and extra_mask.shape[0] != b):
-            raise TypeError("guide_rows: extra_mask must be int64 [b, R, C] or [R, C] with unit column stride")
-        ids_p, ids_sb = extra_ids.data_ptr(), extra_ids.stride(0)
-        mask_p, mask_sr = extra_mask.data_ptr(), extra_mask.stride(-2)
-        mask_sb = extra_mask.stride(0) if extra_mask.dim() == 3 else 0
-    elif extra_mask is not None and extra_ids is None:
-        raise ValueError("guide_rows: extra_mask needs extra_ids")
+    ids_p, ids_sb, mask_p, mask_sb, mask_sr, C = _extras(extra_ids, extra_mask, b, R, "guide_rows", GUIDE_MAX_EXTRA)
     _C.check(_C.load().ls_guide_rows(x.data_ptr(), b, R, V, _dtype(x), x.stride(0), max(x.stride(1), V), tab_p, tab_n,
                                      state.data_ptr(), ids_p, ids_sb, mask_p, mask_sb, mask_sr, C, _stream()), "ls_guide_rows")
     return logits
@@ -784,19 +787,8 @@ def guide_advance(state: torch.Tensor, table: torch.Tensor, ids: torch.Tensor, n
         raise TypeError("guide_advance: state must be a contiguous int32 [b] tensor")
     b = state.shape[0]
     tab_p, tab_n = _guide_table(table, "guide_advance")
-    if ids.dim() == 1:
-        ids = ids.view(b, -1)
-    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] != b:
-        raise TypeError("guide_advance: ids must be int64 [b, n]")
-    if not (1 <= ids.shape[1] <= GUIDE_MAX_EXTRA):
-        raise ValueError(f"guide_advance: {ids.shape[1]} ids per row, 1..{GUIDE_MAX_EXTRA}")
-    if ids.shape[1] > 1 and ids.stride(1) != 1:
-        ids = ids.contiguous()
-    num_p, num_s = None, 0
-    if num is not None:
-        if num.dtype != torch.int64 or num.numel() != b or num.dim() != 1:
-            raise TypeError("guide_advance: num must be int64 [b]")
-        num_p, num_s = num.data_ptr(), num.stride(0)
+    ids = _id_rows(ids, b, "guide_advance", most=GUIDE_MAX_EXTRA)
+    num_p, num_s = _num(num, b, "guide_advance")
     _C.check(_C.load().ls_guide_advance(state.data_ptr(), b, tab_p, tab_n, ids.data_ptr(), ids.shape[1], ids.stride(0), num_p, num_s,
                                         _stream()), "ls_guide_advance")
 
@@ -818,29 +810,15 @@ def ngram_draft(prompt_ids: torch.Tensor, input_len: torch.Tensor, output_ids: t
     is read from the device.  Returns ``info`` int32 [b, 2] = (n, e): the matched length and the end of the occurrence, or
     (0, -1)."""
     _dev(prompt_ids, input_len, output_ids, cache_lens, spec_buffer, info, hist)
-    for t, name in ((prompt_ids, "prompt_ids"), (output_ids, "output_ids")):
-        if t.dtype != torch.int64 or t.dim() != 2 or t.stride(1) != 1:
-            raise TypeError(f"ngram_draft: {name} must be int64 [b, columns] with contiguous rows")
-    b = output_ids.shape[0]
-    if prompt_ids.shape[0] != b or (b > 1 and (prompt_ids.stride(0) < prompt_ids.shape[1] or output_ids.stride(0) < output_ids.shape[1])):
-        raise ValueError("ngram_draft: prompt_ids and output_ids must have one row per batch row, rows apart")
     if not (1 <= gamma <= NGRAM_MAX_GAMMA and 1 <= max_ngram <= NGRAM_MAX_N and 1 <= min_ngram <= max_ngram):
         raise ValueError(f"ngram_draft: gamma={gamma} (1..{NGRAM_MAX_GAMMA}), max_ngram={max_ngram} (1..{NGRAM_MAX_N}), "
                          f"min_ngram={min_ngram} (1..max_ngram)")
+    b, info = _ngram_buffers(prompt_ids, output_ids, len_bound, info, (2,), ((hist, "hist", max_ngram + 1),), "ngram_draft")
     if spec_buffer.dtype != torch.int64 or tuple(spec_buffer.shape) != (b, gamma + 1) or not spec_buffer.is_contiguous():
         raise TypeError(f"ngram_draft: spec_buffer must be a contiguous int64 [{b}, {gamma + 1}] tensor")
-    if int(len_bound) < 1:
-        raise ValueError(f"ngram_draft: len_bound={len_bound}")
-    dev = output_ids.device
-    if info is None:
-        info = torch.empty((b, 2), dtype=torch.int32, device=dev)
-    elif info.dtype != torch.int32 or tuple(info.shape) != (b, 2) or not info.is_contiguous():
-        raise TypeError(f"ngram_draft: info must be a contiguous int32 [{b}, 2] tensor")
-    if hist is not None and (hist.dtype != torch.int64 or tuple(hist.shape) != (b, max_ngram + 1) or not hist.is_contiguous()):
-        raise TypeError(f"ngram_draft: hist must be a contiguous int64 [{b}, {max_ngram + 1}] tensor")
     lib = _C.load()
     need = lib.ls_ngram_workspace_bytes(b, int(len_bound))
-    ws = _ngram_ws.get(dev, max(need, 1))
+    ws = _ngram_ws.get(output_ids.device, max(need, 1))
     _C.check(lib.ls_ngram_draft(prompt_ids.data_ptr(), max(prompt_ids.stride(0), prompt_ids.shape[1]), prompt_ids.shape[1],
                                 _len_i32(input_len, b, "input_len"), output_ids.data_ptr(),
                                 max(output_ids.stride(0), output_ids.shape[1]), output_ids.shape[1],
@@ -867,34 +845,20 @@ def ngram_tree_draft(prompt_ids: torch.Tensor, input_len: torch.Tensor, output_i
     ``hist_nb[z, nb] += 1`` (int64 [b, branches + 1], optional).  ``len_bound``: a HOST-side upper bound of the text lengths.
     Returns ``info`` int32 [b, branches, 2] = (n, e) per slot, (0, -1) for the slots that copy slot 0."""
     _dev(prompt_ids, input_len, output_ids, written, all_spec, tree_mask, info, hist, hist_nb)
-    for t, name in ((prompt_ids, "prompt_ids"), (output_ids, "output_ids")):
-        if t.dtype != torch.int64 or t.dim() != 2 or t.stride(1) != 1:
-            raise TypeError(f"ngram_tree_draft: {name} must be int64 [b, columns] with contiguous rows")
-    b = output_ids.shape[0]
-    if prompt_ids.shape[0] != b or (b > 1 and (prompt_ids.stride(0) < prompt_ids.shape[1] or output_ids.stride(0) < output_ids.shape[1])):
-        raise ValueError("ngram_tree_draft: prompt_ids and output_ids must have one row per batch row, rows apart")
     if not (1 <= gamma <= NGRAM_MAX_GAMMA and 1 <= branches <= NGRAM_TOP and 1 <= max_ngram <= NGRAM_MAX_N
             and 1 <= min_ngram <= max_ngram):
         raise ValueError(f"ngram_tree_draft: gamma={gamma} (1..{NGRAM_MAX_GAMMA}), branches={branches} (1..{NGRAM_TOP}), "
                          f"max_ngram={max_ngram} (1..{NGRAM_MAX_N}), min_ngram={min_ngram} (1..max_ngram)")
+    b, info = _ngram_buffers(prompt_ids, output_ids, len_bound, info, (branches, 2),
+                             ((hist, "hist", max_ngram + 1), (hist_nb, "hist_nb", branches + 1)), "ngram_tree_draft")
     Fn = 1 + branches * gamma
     if all_spec.dtype != torch.int64 or tuple(all_spec.shape) != (b, Fn) or not all_spec.is_contiguous():
         raise TypeError(f"ngram_tree_draft: all_spec must be a contiguous int64 [{b}, {Fn}] tensor")
     if tree_mask.dtype != torch.int64 or tuple(tree_mask.shape) != (b, Fn, Fn) or not tree_mask.is_contiguous():
         raise TypeError(f"ngram_tree_draft: tree_mask must be a contiguous int64 [{b}, {Fn}, {Fn}] tensor")
-    if int(len_bound) < 1:
-        raise ValueError(f"ngram_tree_draft: len_bound={len_bound}")
-    dev = output_ids.device
-    if info is None:
-        info = torch.empty((b, branches, 2), dtype=torch.int32, device=dev)
-    elif info.dtype != torch.int32 or tuple(info.shape) != (b, branches, 2) or not info.is_contiguous():
-        raise TypeError(f"ngram_tree_draft: info must be a contiguous int32 [{b}, {branches}, 2] tensor")
-    for t, name, cols in ((hist, "hist", max_ngram + 1), (hist_nb, "hist_nb", branches + 1)):
-        if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != (b, cols) or not t.is_contiguous()):
-            raise TypeError(f"ngram_tree_draft: {name} must be a contiguous int64 [{b}, {cols}] tensor")
     lib = _C.load()
     need = lib.ls_ngram_tree_workspace_bytes(b, int(len_bound))
-    ws = _ngram_tree_ws.get(dev, max(need, 1))
+    ws = _ngram_tree_ws.get(output_ids.device, max(need, 1))
     _C.check(lib.ls_ngram_tree_draft(prompt_ids.data_ptr(), max(prompt_ids.stride(0), prompt_ids.shape[1]), prompt_ids.shape[1],
                                      _len_i32(input_len, b, "input_len"), output_ids.data_ptr(),
                                      max(output_ids.stride(0), output_ids.shape[1]), output_ids.shape[1],
