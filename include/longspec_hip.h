@@ -557,6 +557,31 @@ int ls_guide_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t s
 int ls_guide_advance(int32_t* state, int b, const int32_t* table, int table_words, const int64_t* ids, int n, int64_t ids_stride_b,
                      const int64_t* num, int64_t num_stride, void* stream);
 
+/* The lift of a byte-level DFA to the tokens of a vocabulary (Guide.from_byte_dfa / Guide.from_regex on a device;
+ * csrc/guide_lift.hip; no counterpart in the reference).  A token's behaviour is the vector state -> state of running its bytes.
+ *   step     16-bit [256, S + 1] on the device, BYTE-major: step[c * (S + 1) + s] = the state behind byte c in state s, S = the
+ *            dead state (step[c, S] = S); S in 1..LS_GUIDE_LIFT_MAX_STATES.  An entry beyond S counts as S.
+ *   blob     uint8 [blob_bytes]: the bytes of all tokens back to back (a valid pointer also where blob_bytes is 0)
+ *   offsets  int32 [T + 1]: token t is blob[offsets[t] : offsets[t + 1]]; a pair that is not 0 <= begin <= end <= blob_bytes
+ *            counts as an empty token.  An empty token is dead from every state.
+ * One launch each, lanes across states, several tokens per wave where S < 64, slices of 64 states beyond; nothing read indexes
+ * memory unclamped.  Exact; no workspace, no atomics, no floating point; every output element is written by every call.
+ *
+ * ls_guide_lift_hash: hashes uint64 [T, 2] = two independent 64-bit hashes of every token's vector (each the wrap-around sum over
+ * s of a mix of (s, the end state of s), summed across lanes by shuffles: equal vectors have equal hashes); alive uint8 [T] = 1
+ * where the token is not empty and some state survives it, else 0.
+ * ls_guide_lift_cols: cols int32 [n, S] = the vector of token ids[i] (int32 [n]; an id outside [0, T): an empty token), -1 = dead.
+ * ls_guide_lift_check: mismatch uint8 [T] = 1 where group[t] >= 0 (int32 [T]) and the token's vector differs from
+ * reps[group[t]] (int32 [C, S], -1 = dead) or group[t] >= C; else 0.  Tokens with group[t] < 0 are not walked.
+ * LS_ERR_INVALID_ARG, before any launch: a null pointer, S outside 1..LS_GUIDE_LIFT_MAX_STATES, T, n or C < 1, blob_bytes < 0. */
+#define LS_GUIDE_LIFT_MAX_STATES 16384
+int ls_guide_lift_hash(const void* step, const void* blob, const int32_t* offsets, int64_t blob_bytes, int T, int S, uint64_t* hashes,
+                       uint8_t* alive, void* stream);
+int ls_guide_lift_cols(const void* step, const void* blob, const int32_t* offsets, int64_t blob_bytes, int T, int S, const int32_t* ids,
+                       int n, int32_t* cols, void* stream);
+int ls_guide_lift_check(const void* step, const void* blob, const int32_t* offsets, int64_t blob_bytes, int T, int S, const int32_t* reps,
+                        int C, const int32_t* group, uint8_t* mismatch, void* stream);
+
 /* The drafter of prompt-lookup (n-gram) speculation (lookup_generate; csrc/lookup.hip; no counterpart in the reference, whose
  * every loop needs a trained draft layer).  The text of batch row z is T = prompt_ids[z, :il] ++ output_ids[z, :w], il =
  * input_len[z] clamped to 0..prompt_cols, w = cache_lens[z] - input_len[z] + 1 clamped to 0..out_cap (the columns written so far,

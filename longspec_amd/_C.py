@@ -118,7 +118,10 @@ SYMBOLS = {
     "ls_ban_rows": (C.c_int, [_P, _I, _I, _I, _I, _L, _L, _P, _I, _P, _L, _I, _P, _P, _I, _P, _L, _P, _L, _L, _I, _P]),
     "ls_guide_rows": (C.c_int, [_P, _I, _I, _I, _I, _L, _L, _P, _I, _P, _P, _L, _P, _L, _L, _I, _P]),
     "ls_guide_advance": (C.c_int, [_P, _I, _P, _I, _P, _I, _L, _P, _L, _P]),
-    "ls_ngram_workspace_bytes": (C.c_size_t, [_I, _L]),
+    "ls_guide_lift_hash": (C.c_int, [_P, _P, _P, _L, _I, _I, _P, _P, _P]),
+    "ls_guide_lift_cols": (C.c_int, [_P, _P, _P, _L, _I, _I, _P, _I, _P, _P]),
+    "ls_guide_lift_check": (C.c_int, [_P, _P, _P, _L, _I, _I, _P, _I, _P, _P, _P]),
+    "ls_ngram_workspace_bytes":(C.c_size_t, [_I, _L]),
     "ls_ngram_draft": (C.c_int, [_P, _L, _I, _P, _P, _L, _I, _P, _I, _L, _I, _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
     "ls_ngram_tree_workspace_bytes": (C.c_size_t, [_I, _L]),
     "ls_ngram_tree_draft": (C.c_int, [_P, _L, _I, _P, _P, _L, _I, _P, _I, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),

@@ -21,6 +21,10 @@ its path.  ``s < 0``: the row is dead and keeps its bits -- its parent's logits 
 accepted.  Otherwise every ``v`` in ``[0, V)`` with ``walk(s, v) < 0`` gets the type's ``-inf`` pattern; every other element
 keeps its bits.  A live row in which everything is forbidden is the caller's error (``table`` refuses the reachable ones).
 
+Where guides come from: the constructor (any table), ``Guide.choice`` (one of these answers, then EOS), ``Guide.from_byte_dfa``
+(a byte-level DFA lifted to the tokens of a vocabulary, on the host or -- ``device=`` -- by ``ops.guide_lift``) and
+``Guide.from_regex`` (``longspec_amd/regex.py`` compiles the pattern to the byte DFA; then the lift, then EOS).
+
 The device side (``ops.guide_rows`` / ``ops.guide_advance``) reads one int32 table, built once per decode state:
 
     [0] S   [1] C   [2] start   [3] vocab   [4] the word count   [5 : 8] reserved (0)
@@ -43,6 +47,7 @@ MAX_CLASSES = 16384              # C (LS_GUIDE_MAX_CLASSES): a state's allow bit
 MAX_CELLS = 1 << 24              # S * C (LS_GUIDE_MAX_CELLS): the transition area is at most 64 MB
 HEADER_WORDS = 8                 # (LS_GUIDE_HEADER_WORDS)
 NO_CLASS = 0xFFFF                # the 16-bit class of a forbidden id (LS_GUIDE_NO_CLASS)
+LIFT_MAX_STATES = 16384          # byte-DFA states the device lifts (LS_GUIDE_LIFT_MAX_STATES)
 
 
 def _int_array(v, what, ndim):
@@ -223,10 +228,13 @@ class Guide:
         return cls(nx, tc, 0)
 
     @classmethod
-    def from_byte_dfa(cls, byte_next, token_bytes, start=0) -> "Guide":
+    def from_byte_dfa(cls, byte_next, token_bytes, start=0, device=None) -> "Guide":
         """Lift a byte-level DFA (``byte_next`` int [S, 256], -1 = dead) to the tokens of a vocabulary (``token_bytes``: the byte
         string of every id; an empty one: the token is forbidden).  A token's behaviour is the vector state -> state of running
-        its bytes; tokens with the same vector share a class, tokens that are dead from every state are forbidden."""
+        its bytes; tokens with the same vector share a class, tokens that are dead from every state are forbidden.  ``device``:
+        None walks every token from every state on the host; a GPU device runs the lift there (``ops.guide_lift``: hashes of the
+        vectors, exact vectors of one token per hash group, every token verified) and gives an equal object; a DFA beyond
+        ``LIFT_MAX_STATES`` states is lifted on the host."""
         bn = _int_array(byte_next, "byte_next", 2)
         S = bn.shape[0]
         if bn.shape[1] != 256 or S < 1:
@@ -241,6 +249,8 @@ class Guide:
         T = len(token_bytes)
         lens = np.fromiter((len(t) for t in token_bytes), dtype=np.int64, count=T)
         flat = np.frombuffer(b"".join(bytes(t) for t in token_bytes), dtype=np.uint8)
+        if device is not None and torch.device(device).type == "cuda" and T >= 1 and S <= LIFT_MAX_STATES and flat.size < 2 ** 31:
+            return cls._lifted_on_device(bn, lens, flat, start, torch.device(device))
         offs = np.concatenate(([0], np.cumsum(lens)))[:-1]
         step = np.vstack([bn, np.full((1, 256), S, dtype=np.int64)])          # row S: the dead state, as an index
         step[step < 0] = S
@@ -266,6 +276,58 @@ class Guide:
         else:
             nx = np.full((S, 1), -1, dtype=np.int64)
         return cls(nx, tc, start)
+
+    @classmethod
+    def _lifted_on_device(cls, bn, lens, flat, start, device) -> "Guide":
+        """``from_byte_dfa`` through ``ops.guide_lift``: the step table byte-major with the dead state as column S."""
+        from . import ops
+        S = bn.shape[0]
+        step = np.full((256, S + 1), S, dtype=np.int16)
+        step[:, :S] = np.where(bn < 0, S, bn).T
+        offsets = np.zeros(lens.size + 1, dtype=np.int32)
+        np.cumsum(lens, out=offsets[1:])
+        with torch.cuda.device(device):
+            tc, vecs = ops.guide_lift(torch.from_numpy(step).to(device), torch.from_numpy(flat.copy()).to(device),
+                                      torch.from_numpy(offsets).to(device))
+        nx = vecs.T if vecs.shape[0] else np.full((S, 1), -1, dtype=np.int64)
+        return cls(nx, tc, start)
+
+    @classmethod
+    def from_regex(cls, pattern, token_bytes, eos_id: int, device=None, max_states: int = 4096) -> "Guide":
+        """The text, as the bytes of its tokens, must match ``pattern`` as a whole and is then ended by ``eos_id``: the pattern
+        compiled to a byte DFA (``longspec_amd.regex.compile``: the subset and its errors), lifted to the vocabulary
+        (``from_byte_dfa``, on ``device`` where given) and ended as ``choice`` ends its sequences -- one more class for
+        ``eos_id`` (whatever its bytes are) and one more state F, ``next[s, eos] = F`` in every accepting s, F looping on
+        ``eos_id``.  Every transition into a state from which F cannot be reached over the tokens of this vocabulary is cleared,
+        so no text gets stuck: a finished text always matches.  ValueError where the start is such a state."""
+        from . import regex
+        if isinstance(eos_id, bool) or not isinstance(eos_id, (int, np.integer)) or not (0 <= eos_id < 2 ** 31):
+            raise ValueError(f"Guide: eos_id {eos_id!r} is not a token id (0 .. 2^31 - 1)")
+        dfa = regex.compile(pattern, max_states=max_states)
+        g = cls.from_byte_dfa(dfa.next, token_bytes, 0, device=device)
+        S, C = g.next.shape
+        nx = np.full((S + 1, C + 1), -1, dtype=np.int64)
+        nx[:S, :C] = g.next
+        nx[:S, C][dfa.accepting] = S
+        nx[S, C] = S
+        tc = np.full(max(g.token_class.size, int(eos_id) + 1), -1, dtype=np.int64)
+        tc[:g.token_class.size] = g.token_class
+        tc[eos_id] = C
+        used = np.zeros(C + 1, dtype=bool)
+        used[tc[tc >= 0]] = True
+        live = np.where(used[None, :], nx, -1)                                # transitions some token takes
+        good = np.zeros(S + 1, dtype=bool)
+        good[S] = True
+        while True:
+            more = good | np.where(live >= 0, good[np.maximum(live, 0)], False).any(axis=1)
+            if (more == good).all():
+                break
+            good = more
+        if not good[0]:
+            raise ValueError(f"Guide: the vocabulary cannot spell the language of {pattern!r}: no sequence of its tokens "
+                             f"followed by eos_id = {eos_id} matches")
+        nx[(nx >= 0) & ~good[np.maximum(nx, 0)]] = -1
+        return cls(nx, tc, 0)
 
     # --------------------------------------------------------------------------------------------------------------------
     def save(self, path):

@@ -25,6 +25,8 @@ One function per reference seam of the draft-then-verify round:
                          row's ordered path (ban=; no counterpart)
   guide_rows / guide_advance   guided decoding: the tokens a DFA over token ids forbids in the state behind the row's path, and
                          the per-row committed state they start from (guide=; no counterpart)
+  guide_lift (_hash / _cols / _check)   the classes of a vocabulary's tokens under a byte-level DFA, the set-up of a guide
+                         (Guide.from_byte_dfa / Guide.from_regex with a device; no counterpart)
   tree_commit / tree_commit_stochastic   end of a round at temperature 0 / > 0  llama_glide.py:1093-1121
   linear / linear_multi / mlp_gate_up   the projections of a decode pass (M <= 80 token rows):
                          q/k/v/o_proj llama.py:361-363,390, LlamaMLP (qwen2.py:218-230), lm_head llama_glide.py:1091
@@ -791,6 +793,133 @@ def guide_advance(state: torch.Tensor, table: torch.Tensor, ids: torch.Tensor, n
     num_p, num_s = _num(num, b, "guide_advance")
     _C.check(_C.load().ls_guide_advance(state.data_ptr(), b, tab_p, tab_n, ids.data_ptr(), ids.shape[1], ids.stride(0), num_p, num_s,
                                         _stream()), "ls_guide_advance")
+
+
+GUIDE_LIFT_MAX_STATES = 16384   # S of a byte DFA the device lifts (LS_GUIDE_LIFT_MAX_STATES): its states are 16-bit table entries
+GUIDE_MAX_CLASSES = 16384       # C of a guide (longspec_amd/guide.py, LS_GUIDE_MAX_CLASSES)
+
+
+def _lift_operands(step, blob, offsets, who):
+    """(step pointer, blob pointer, offsets pointer, blob bytes, T, S) of the lift's operands (``ls_guide_lift_*``)."""
+    _dev(step, blob, offsets)
+    if step.dtype != torch.int16 or step.dim() != 2 or step.shape[0] != 256 or not step.is_contiguous() \
+            or not (1 <= step.shape[1] - 1 <= GUIDE_LIFT_MAX_STATES):
+        raise TypeError(f"{who}: step must be a contiguous int16 [256, S + 1] tensor (byte-major, S = the dead state) with S in "
+                        f"1..{GUIDE_LIFT_MAX_STATES}")
+    if blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous():
+        raise TypeError(f"{who}: blob must be a contiguous uint8 [bytes] tensor")
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_contiguous():
+        raise TypeError(f"{who}: offsets must be a contiguous int32 [T + 1] tensor, T >= 1")
+    # (an empty blob has no storage to point at: any valid address will do, nothing is read through it)
+    return step.data_ptr(), blob.data_ptr() if blob.numel() else step.data_ptr(), offsets.data_ptr(), blob.numel(), \
+        offsets.numel() - 1, step.shape[1] - 1
+
+
+def guide_lift_hash(step: torch.Tensor, blob: torch.Tensor, offsets: torch.Tensor):
+    """Two 64-bit hashes of every token's behaviour vector under a byte DFA and its alive flag (``ls_guide_lift_hash``, one
+    launch): ``(hashes int64 [T, 2], alive uint8 [T])``.  ``step`` int16 [256, S + 1] byte-major with S the dead state, ``blob``
+    uint8 the bytes of all tokens, ``offsets`` int32 [T + 1].  Equal vectors have equal hashes; an empty token is not alive."""
+    sp, bp, op, nb, T, S = _lift_operands(step, blob, offsets, "guide_lift_hash")
+    hashes = torch.empty((T, 2), dtype=torch.int64, device=step.device)
+    alive = torch.empty((T,), dtype=torch.uint8, device=step.device)
+    _C.check(_C.load().ls_guide_lift_hash(sp, bp, op, nb, T, S, hashes.data_ptr(), alive.data_ptr(), _stream()), "ls_guide_lift_hash")
+    return hashes, alive
+
+
+def guide_lift_cols(step: torch.Tensor, blob: torch.Tensor, offsets: torch.Tensor, ids: torch.Tensor,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The exact behaviour vectors of the tokens ``ids`` (contiguous int32 [n], n >= 1), int32 [n, S] with -1 = dead
+    (``ls_guide_lift_cols``, one launch), into ``out`` (contiguous int32 [n, S]) where given."""
+    sp, bp, op, nb, T, S = _lift_operands(step, blob, offsets, "guide_lift_cols")
+    _dev(ids, out)
+    if ids.dtype != torch.int32 or ids.dim() != 1 or ids.numel() < 1 or not ids.is_contiguous():
+        raise TypeError("guide_lift_cols: ids must be a contiguous int32 [n] tensor, n >= 1")
+    n = ids.numel()
+    if out is None:
+        out = torch.empty((n, S), dtype=torch.int32, device=step.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (n, S) or not out.is_contiguous():
+        raise TypeError(f"guide_lift_cols: out must be a contiguous int32 [{n}, {S}] tensor")
+    _C.check(_C.load().ls_guide_lift_cols(sp, bp, op, nb, T, S, ids.data_ptr(), n, out.data_ptr(), _stream()), "ls_guide_lift_cols")
+    return out
+
+
+def guide_lift_check(step: torch.Tensor, blob: torch.Tensor, offsets: torch.Tensor, reps: torch.Tensor,
+                     group: torch.Tensor) -> torch.Tensor:
+    """uint8 [T]: 1 where token t has ``group[t] >= 0`` (contiguous int32 [T]) and its behaviour vector is not
+    ``reps[group[t]]`` (contiguous int32 [C, S], -1 = dead), else 0 (``ls_guide_lift_check``, one launch)."""
+    sp, bp, op, nb, T, S = _lift_operands(step, blob, offsets, "guide_lift_check")
+    _dev(reps, group)
+    if reps.dtype != torch.int32 or reps.dim() != 2 or reps.shape[0] < 1 or reps.shape[1] != S or not reps.is_contiguous():
+        raise TypeError(f"guide_lift_check: reps must be a contiguous int32 [C, {S}] tensor, C >= 1")
+    if group.dtype != torch.int32 or tuple(group.shape) != (T,) or not group.is_contiguous():
+        raise TypeError(f"guide_lift_check: group must be a contiguous int32 [{T}] tensor")
+    mismatch = torch.empty((T,), dtype=torch.uint8, device=step.device)
+    _C.check(_C.load().ls_guide_lift_check(sp, bp, op, nb, T, S, reps.data_ptr(), reps.shape[0], group.data_ptr(),
+                                           mismatch.data_ptr(), _stream()), "ls_guide_lift_check")
+    return mismatch
+
+
+def guide_lift(step: torch.Tensor, blob: torch.Tensor, offsets: torch.Tensor, *, _hash_bits: int = 128, _stats=None):
+    """The classes of a vocabulary under a byte DFA: ``(token_class int64 [T], vectors int64 [C, S])`` as numpy arrays on the
+    host -- tokens with the same behaviour vector share a class, ``vectors[c]`` is the class's vector (-1 = dead), a token that
+    is empty or dead from every state has class -1, and the classes are numbered as ``np.unique(axis=0)`` numbers the rows of
+    the full [T, S] matrix (lexicographically), which is never built: the device hashes every vector (``guide_lift_hash``), the
+    alive tokens are grouped by hash, one representative per group is walked exactly (``guide_lift_cols``), every token is
+    checked against its group's representative (``guide_lift_check``), and a token that differs -- a hash collision -- is walked
+    exactly and regrouped on the host.  ValueError where the groups outnumber ``GUIDE_MAX_CLASSES``.  ``_hash_bits`` below 128
+    keeps only that many low bits of the first hash (0: one group): the tests' way into the collision path.  ``_stats``: a dict
+    that receives ``groups`` and ``mismatches``."""
+    import numpy as np
+    _, _, _, _, T, S = _lift_operands(step, blob, offsets, "guide_lift")
+    if isinstance(_hash_bits, bool) or not isinstance(_hash_bits, int) or not (0 <= _hash_bits <= 128):
+        raise ValueError(f"guide_lift: _hash_bits must be 0..128, got {_hash_bits!r}")
+    too_many = lambda n: ValueError(f"Guide: the vocabulary has {n} or more distinct behaviours under this DFA, more than "
+                                    f"{GUIDE_MAX_CLASSES} classes")
+    hashes, alive = guide_lift_hash(step, blob, offsets)
+    alive_ids = alive.nonzero().view(-1)
+    token_class = np.full(T, -1, dtype=np.int64)
+    if _stats is not None:
+        _stats.update(groups=0, mismatches=0)
+    if alive_ids.numel() == 0:
+        return token_class, np.zeros((0, S), dtype=np.int64)
+    keys = hashes[alive_ids]
+    if _hash_bits < 128:
+        bits = min(_hash_bits, 64)
+        low = keys[:, 0] & ((1 << bits) - 1 if bits < 63 else -1 if bits == 64 else 2 ** 63 - 1)
+        keys = torch.stack([low, torch.zeros_like(low)], dim=1)
+    _, inverse = torch.unique(keys, dim=0, return_inverse=True)
+    G = int(inverse.max()) + 1
+    if G > GUIDE_MAX_CLASSES:
+        raise too_many(G)
+    place = torch.arange(alive_ids.numel(), device=step.device)
+    first = torch.full((G,), alive_ids.numel(), dtype=torch.int64, device=step.device).scatter_reduce_(0, inverse, place, "amin")
+    reps = guide_lift_cols(step, blob, offsets, alive_ids[first].to(torch.int32))
+    group = torch.full((T,), -1, dtype=torch.int32, device=step.device)
+    group[alive_ids] = inverse.to(torch.int32)
+    odd = guide_lift_check(step, blob, offsets, reps, group).nonzero().view(-1)
+    vectors = reps.cpu().numpy()
+    group = group.cpu().numpy().astype(np.int64)
+    if _stats is not None:
+        _stats.update(groups=G, mismatches=int(odd.numel()))
+    if odd.numel():                                                # collisions: exact vectors, at most GUIDE_MAX_CLASSES at a time
+        known = {v.tobytes(): c for c, v in enumerate(vectors)}
+        extra = []
+        for chunk in odd.split(GUIDE_MAX_CLASSES):
+            vs = guide_lift_cols(step, blob, offsets, chunk.to(torch.int32)).cpu().numpy()
+            for t, v in zip(chunk.cpu().tolist(), vs):
+                c = known.get(v.tobytes())
+                if c is None:
+                    c = known[v.tobytes()] = len(known)
+                    extra.append(v)
+                    if len(known) > GUIDE_MAX_CLASSES:
+                        raise too_many(len(known))
+                group[t] = c
+        vectors = np.concatenate([vectors, np.stack(extra)]) if extra else vectors
+    vectors, rank = np.unique(vectors, axis=0, return_inverse=True)     # the numbering of np.unique on the full matrix
+    rank = np.asarray(rank).reshape(-1)
+    live = group >= 0
+    token_class[live] = rank[group[live]]
+    return token_class, vectors.astype(np.int64)
 
 
 _ngram_ws = _Workspace()     # its own buffer, as _sample_ws: a captured round holds its address
