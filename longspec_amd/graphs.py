@@ -1,8 +1,9 @@
-"""HIP-graph replay of a decode loop's device function: the mechanics ``vanilla_step`` and ``tree_round`` share.
+"""HIP-graph replay of a decode loop's device function: what ``vanilla_step``, ``lookup_round`` and the tree rounds share.
 
-A loop (``llama_glide.py``) keeps its policy -- when a call is eligible, what its keys are, when a key is warmed, captured and
-replayed -- and leaves to ``GraphReplayer`` the capture stream, the memory pool, the tier a capture is sized for, the entries
-per key, the counters and what happens when any of it fails."""
+A loop (``llama_glide.py``) keeps its policy -- when a call is eligible, what its keys are, the hints of an eager call, whether
+a failure switches ``use_graphs`` off -- and leaves to ``GraphReplayer`` the round driver (``run``: warm-up, capture, replay), the
+capture stream, the memory pool, the tier a capture is sized for, the entries per key, the counters and what happens when any
+of it fails."""
 from __future__ import annotations
 
 import warnings
@@ -25,7 +26,8 @@ class GraphReplayer:
         self.bound, self.tiers, self.captures = bound, tiers, 0
         self.entries, self.stream, self.pool = {}, None, None
         self.disabled = False            # after a failure: the loop runs eagerly from then on
-        self.issued = False              # inside / behind a guard: this call's device work is already on the capture stream
+        self.failed = False              # behind a guard: this call was the one that failed
+        self.issued = False             # inside / behind a guard: this call's device work is already on the capture stream
         self.result = None               # ... and this is what it returned
 
     def roll_over(self, reached: int):
@@ -75,20 +77,39 @@ class GraphReplayer:
         graph.replay()
         return result
 
+    def run(self, key, device_fn, reached: int, same_call: bool = False):
+        """One call of a loop on the graph path, the generation at ``reached`` emitted tokens: ``key`` absent -> warm-up,
+        warm -> capture + replay, captured -> replay.  ``same_call`` (a loop with one key: the vanilla step, the lookup round)
+        captures behind the warm-up in the call that warms; by default (one key per accepted count) the first call with a key
+        warms and the second captures and replays.  Either way the warm-up IS the call's device work and never runs twice.
+        Returns what ``device_fn`` returned, or None when the work has still to run, eagerly: after a failure (``failed``) in
+        front of the warm-up -- tier sizing, ``wait_stream`` -- or in a replay."""
+        with self.guard():
+            self.roll_over(reached)
+            if key not in self.entries:
+                result = self.warm(key, device_fn)
+                if same_call:
+                    self.capture(key, device_fn)
+                return result
+            if not self.captured(key):
+                self.capture(key, device_fn)
+            return self.replay(key)
+        return self.result if self.issued else None
+
     @contextmanager
     def guard(self):
         """Capture is an optimisation: an environment that cannot do it runs eagerly.  Any exception of the above inside this
-        block (but one raised while a capture is open) becomes one warning and ``disabled``; the block is left, and
+        block (but one raised while a capture is open) becomes one warning, ``failed`` and ``disabled``; the block is left, and
         ``issued`` tells the caller whether the call's device work has run all the same (then ``result`` is its result, and
         the main stream has been made to wait for it) or is still to be done eagerly."""
-        self.issued, self.result = False, None
+        self.issued, self.result, self.failed = False, None, False
         try:
             yield
         except Exception as e:
             if torch.cuda.is_current_stream_capturing():
                 raise
             warnings.warn(f"HIP-graph capture of the {self.what} failed ({type(e).__name__}: {e}); running eagerly")
-            self.disabled = True
+            self.disabled = self.failed = True
             self.entries = {}
             if self.issued:
                 torch.cuda.current_stream().wait_stream(self.stream)

@@ -209,6 +209,37 @@ def _sync(t: torch.Tensor):
         torch.cuda.synchronize(t.device)
 
 
+def _chain_round_host(st, state) -> bool:
+    """The host half of a chain-shaped round (``chain_round``, ``lookup_round``): the round's ONE host read, state [bsz, 2] =
+    (correct_len, EOS hit | 2 * stop hit), onto the host mirrors.  False = stop: the buffer cannot take another round, or a
+    hit (a ``stop=`` match leaves the counters as they are)."""
+    state = state.tolist()
+    n_ok, hit = state[0][0], any(row[1] for row in state)
+    st.stopped = any(row[1] & 2 for row in state)                     # ops.stop_scan raised bit 1
+    st.count += n_ok - 1
+    st.num += st.bsz
+    st.emitted += n_ok
+    if st.emitted - 1 + st.gamma + 2 > st.output_ids.size(1):
+        return False
+    return not hit
+
+
+def _tree_round_host(st, state) -> bool:
+    """The host half of a tree-shaped round (``tree_round``, ``_lookup_tree_round``): the round's ONE host read, state [bsz, 2]
+    = (acc_num, EOS hit | 2 * stop hit), onto the host mirrors; False as above (:1118, :1120)."""
+    state = state.tolist()
+    a, hit = state[0][0], any(row[1] for row in state)
+    st.stopped = any(row[1] & 2 for row in state)
+    st.acc_ids = st.acc_pad[:, :a]
+    st.a = a
+    st.emitted += a
+    st.count += a - 1
+    st.num += st.bsz
+    if st.emitted + st.gamma + 2 > st.output_ids.size(1):
+        return False
+    return not hit
+
+
 class LlamaGlide(LlamaForCausalLM):
     """``LlamaGlide`` (``llama_glide.py:471-1245``).  ``LlamaGlide(config, target_model_path,
     glide_path=None)`` -- the reference's signature -- loads the target and the draft checkpoint (local
@@ -368,6 +399,27 @@ class LlamaGlide(LlamaForCausalLM):
             layer.self_attn.shard = None
         self.glide.cross_attn.shard = None
 
+    def _prefill_target(self, input_ids, prompt_length, exec_type="prefill"):
+        """The target's prefill of every front door (:954-960): returns (the logits of each row's last prompt token, int32
+        ``cache_lens`` [bsz] = ``prompt_length``, a tensor of the caller's own)."""
+        bsz, P = input_ids.size(0), int(input_ids.size(1))
+        self._set_hints(P, P)
+        hidden_states = self.model.forward(input_ids, exec_type=exec_type).last_hidden_state
+        rows = torch.arange(bsz, device=input_ids.device)
+        logits = self.lm_head(hidden_states[rows, prompt_length - 1, :])
+        return logits, input_ids.new_zeros((bsz)).int() + prompt_length.to(input_ids.device).int()
+
+    def _prefill_draft(self, input_ids, lens):
+        """The glide prefill (:968-975) over the target's last-layer KV of ``lens`` [bsz] int32 rows; ``lens=None``: the
+        draft cache's prompt rows alone (``_sharded_prefill``)."""
+        hidden_states = self.model.embed_tokens(input_ids)
+        position_ids = torch.arange(0, input_ids.size(1), device=input_ids.device)[None, :]
+        position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
+        if lens is None:
+            return self.glide.prefill_cache_only(hidden_states, position_embeddings)
+        self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
+                   cache_lens=lens.clone(), llm_kv_len=lens.clone(), exec_type="prefill")
+
     @torch.inference_mode()
     def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645, sampling=None,
                          penalties=None, logprobs=None, stop=None, ban=None, guide=None):                                      # :552-585
@@ -381,17 +433,12 @@ class LlamaGlide(LlamaForCausalLM):
         rules = self._rules(input_ids.device, None, None, sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop,
                             ban=ban, guide=guide)
         self._clear_shard()
-        bsz = input_ids.size(0)
+        bsz, P = input_ids.size(0), int(input_ids.size(1))
         output_ids = input_ids.new_zeros((bsz, max_gen_len))
         self.set_max_gen_len(max_gen_len)
-        cache_lens = input_ids.new_zeros((bsz)).int()
-        P = int(input_ids.size(1))
-        self._set_hints(P, P)
-        hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
         input_len = prompt_length
-        rows = torch.arange(bsz, device=input_ids.device)
-        output_ids[:, 0] = rules.first_token(self.lm_head(hidden_states[rows, input_len - 1, :]), input_len, input_ids)
-        cache_lens += input_len.int()
+        logits, cache_lens = self._prefill_target(input_ids, input_len)
+        output_ids[:, 0] = rules.first_token(logits, input_len, input_ids)
         num = 0
         eos = self._stop_id(eos_id, "vanilla")
         _sync(input_ids)
@@ -480,20 +527,14 @@ class LlamaGlide(LlamaForCausalLM):
         """Decode one token.  On a GPU the step is captured into a HIP graph after GRAPH_AFTER eager steps and replayed."""
         vs.step += 1
         if vs.use_graphs and vs.step > self.GRAPH_AFTER:
-            rp, step = vs.replayer, partial(self._vanilla_device, vs)
-            with rp.guard():
-                rp.roll_over(vs.step + 1)                             # (step s reads s rows beyond the prompt's)
-                if rp.captured(None):
-                    rp.replay(None)
-                else:
-                    rp.warm(None, step)                               # the warm-up step is this call's token
-                    rp.capture(None, step)
+            rp = vs.replayer
+            rp.run(None, partial(self._vanilla_device, vs), vs.step + 1, same_call=True)     # (step s reads s rows past the prompt)
+            if not rp.failed:
                 return
             vs.use_graphs = False
             if rp.issued:                                             # the warm-up step already produced this call's token
                 return
-            # anything else (a failure in front of the warm-up step -- tier sizing, wait_stream -- or in a later
-            # replay()) has not decoded this call's token: fall through to the eager step
+            # any other failure has not decoded this call's token: fall through to the eager step
         self._set_hints(vs.P + vs.step, vs.P + vs.step)
         self._vanilla_device(vs)
 
@@ -528,25 +569,15 @@ class LlamaGlide(LlamaForCausalLM):
                             stop=stop, ban=ban, guide=guide)
         magic = drafter == "magicdec"      # (temperature > 0: the same rejection block in both loops, :715-736 = :854-875)
         self._clear_shard()
-        bsz = input_ids.size(0)
+        bsz, P = input_ids.size(0), int(input_ids.size(1))
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
-        dev = input_ids.device
         self.set_max_gen_len(max_gen_len + 128)
         if not magic:
             self.glide.set_max_gen_len(max_gen_len + 128)
-        P = int(input_ids.size(1))
-        self._set_hints(P, P)
-        hidden_states = self.model.forward(input_ids, exec_type="magicdec_prefill" if magic else "prefill").last_hidden_state
         input_len = prompt_length
-        rows = torch.arange(bsz, device=dev)
-        logits = self.lm_head(hidden_states[rows, input_len - 1, :])
-        cache_lens = input_ids.new_zeros((bsz)).int() + input_len.int()
-        if not magic:                                    # glide prefill
-            hidden_states = self.model.embed_tokens(input_ids)
-            position_ids = torch.arange(0, input_ids.size(1), device=dev)[None, :]
-            position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
-            self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
-                       cache_lens=cache_lens.clone(), llm_kv_len=cache_lens.clone(), exec_type="prefill")
+        logits, cache_lens = self._prefill_target(input_ids, input_len, "magicdec_prefill" if magic else "prefill")
+        if not magic:
+            self._prefill_draft(input_ids, cache_lens)
         first = rules.first_token(logits, input_len, input_ids)
         st = self.begin_chain_decode(first, cache_lens, input_len, P, gamma, max_gen_len, eos_id, temperature, drafter,
                                      first_logits=logits, prompt_ids=input_ids, rules=rules)
@@ -574,34 +605,70 @@ class LlamaGlide(LlamaForCausalLM):
         accepts fill their log-prob columns.  A ``stop=`` match ends the loop with that round; the host counters ``count`` /
         ``num`` / ``emitted`` are not rolled back."""
         bsz = first_token.size(0)
-        dev = first_token.device
         if rules is None:
-            rules = self._rules(dev, temperature, self.model.layers[-1].self_attn.shard, sampling=sampling, penalties=penalties,
-                                logprobs=logprobs, stop=stop, ban=ban, guide=guide)
+            rules = self._rules(first_token.device, temperature, self.model.layers[-1].self_attn.shard, sampling=sampling,
+                                penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide)
         if drafter != "magicdec":
             self._head_of_draft_passes()                # the draft passes' head and its pack exist before the first round
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
-                             max_gen_len=max_gen_len, count=0, num=0, emitted=1, double_flag=False)
-        st.output_ids = first_token.new_zeros((bsz, max_gen_len + gamma))
-        st.spec_mask = first_token.new_zeros((bsz, max_gen_len + gamma))
-        st.output_ids[:, 0] = first_token
-        st.cache_lens = cache_lens
-        st.draft_cache_lens = cache_lens.clone()
-        st.input_len = input_len
-        st.input_len_i32 = input_len.to(device=dev, dtype=torch.int32).view(bsz).contiguous()
-        st.spec_buffer = st.output_ids.new_zeros((bsz, gamma + 1))
-        st.spec_buffer[:, 0] = st.output_ids[:, 0]
+                             max_gen_len=max_gen_len, double_flag=False)
         # temperature > 0 (:639-640,704,709): the draft's fp32 logits of every step, for the rejection test of :716-736
         st.spec_logits = None
         if temperature > 0:
             assert first_logits is not None
             st.spec_logits = first_logits.new_zeros((bsz, gamma + 1, first_logits.size(-1)), dtype=torch.float32)
             st.spec_logits[:, 0] = first_logits
-        st.next_spec_start_token = st.output_ids.new_zeros((bsz, 2))
-        st.next_spec_start_token[:, 0] = st.output_ids[:, 0]
-        st.eos = self._stop_id(eos_id, "spec")
         st.stream_rows = self.model.layers[0].self_attn.STREAM_SINK + self.model.layers[0].self_attn.STREAM_WINDOW
+        self._chain_state(st, first_token, cache_lens, input_len, eos_id, prompt_ids, rules)
+        st.next_spec_start_token[:, 0] = st.output_ids[:, 0]       # the first draft pass starts from it
+        return st
+
+    def _chain_state(self, st, first_token, cache_lens, input_len, eos_id, prompt_ids, rules):
+        """What the states of the chain-shaped loops (``begin_chain_decode``, ``begin_lookup_decode``) share, onto ``st``
+        (``gamma``, ``bsz``, ``max_gen_len`` set): the text and its mask, gamma columns wider than the budget, the round's
+        ``spec_buffer``, the lengths, what ``chain_commit`` keeps for the next round, the host counters and the rules."""
+        bsz, gamma = st.bsz, st.gamma
+        st.count, st.num, st.emitted = 0, 0, 1
+        st.output_ids = first_token.new_zeros((bsz, st.max_gen_len + gamma))
+        st.spec_mask = first_token.new_zeros((bsz, st.max_gen_len + gamma))
+        st.output_ids[:, 0] = first_token
+        st.cache_lens = cache_lens
+        st.draft_cache_lens = cache_lens.clone()            # (a drafter without a cache of its own: chain_commit's scratch)
+        st.input_len = input_len
+        st.input_len_i32 = input_len.to(device=first_token.device, dtype=torch.int32).view(bsz).contiguous()
+        st.spec_buffer = st.output_ids.new_zeros((bsz, gamma + 1))
+        st.spec_buffer[:, 0] = st.output_ids[:, 0]
+        st.next_spec_start_token = st.output_ids.new_zeros((bsz, 2))
+        st.eos = self._stop_id(eos_id, "spec")
         rules.bind(st, first_token, prompt_ids, input_len, (st.cache_lens, st.input_len_i32, 1, 0), gamma=gamma)
+        return st
+
+    def _tree_state(self, st, first_token, cache_lens, prompt_len, width: int, eos_id, prompt_ids, rules):
+        """What the states of the tree-shaped loops (``begin_tree_decode``, ``_begin_lookup_tree``) share, onto ``st``
+        (``gamma``, ``Fn``, ``bsz``, ``dev``, ``num`` set): the filled text of ``width`` columns (:937, G8) and its mask, the
+        tree (``all_spec``, ``tree_mask``, ``history_logp_sum``: tree_commit resets them together), the accepted ids of the
+        last round, the host mirrors, an int32 ``cache_lens`` of the state's own (the tree operators advance the lengths in
+        place) and the rules."""
+        bsz, Fn, dev = st.bsz, st.Fn, st.dev
+        st.fill = self._tree_output_fill(eos_id)
+        st.output_ids = torch.full((bsz, width), st.fill, dtype=torch.int64, device=dev)
+        st.spec_mask = torch.zeros((bsz, width), dtype=torch.int64, device=dev)
+        st.output_ids[:, 0] = first_token
+        st.cache_lens = cache_lens.to(torch.int32).clone()
+        st.count = 0
+        st.all_spec = torch.zeros((bsz, Fn), dtype=torch.int64, device=dev)
+        st.all_spec[:, 0] = first_token
+        st.tree_mask = torch.zeros((bsz, Fn, Fn), dtype=torch.int64, device=dev)
+        st.tree_mask[:, :, 0] = 1
+        st.history_logp_sum = torch.zeros((bsz, Fn), dtype=torch.float32, device=dev)
+        st.acc_pad = torch.zeros((bsz, st.gamma + 1), dtype=torch.int64, device=dev)
+        st.acc_pad[:, 0] = first_token
+        st.acc_ids = st.acc_pad[:, :1]
+        st.a = 1                              # host mirror of acc_num (G9: the pad id is outside the vocab)
+        st.emitted = 1                        # host mirror of emitted_dev: columns of output_ids written so far
+        st.emitted_dev = torch.ones((bsz,), dtype=torch.int32, device=dev)
+        st.eos = self._stop_id(eos_id, "tree")
+        rules.bind(st, first_token, prompt_ids, prompt_len, (st.emitted_dev, None, 0, st.fill))
         return st
 
     def chain_round(self, st) -> bool:
@@ -610,9 +677,9 @@ class LlamaGlide(LlamaForCausalLM):
         full); on a state a ``stop=`` match has ended, False at once."""
         if st.stopped:
             return False
-        gamma, magic, bsz, P = st.gamma, st.magic, st.bsz, st.P
+        gamma, magic, P = st.gamma, st.magic, st.P
         dev = st.output_ids.device
-        output_ids, cache_lens, draft_cache_lens = st.output_ids, st.cache_lens, st.draft_cache_lens
+        cache_lens, draft_cache_lens = st.cache_lens, st.draft_cache_lens
         spec_buffer, spec_logits, next_spec_start_token = st.spec_buffer, st.spec_logits, st.next_spec_start_token
         bound = P + st.emitted + gamma + 2
         self._set_hints(bound, bound)
@@ -656,17 +723,10 @@ class LlamaGlide(LlamaForCausalLM):
                 spec_buffer[:, spec_steps + 1] = self.ops.argmax_rows(current_logp).view(-1,)
                 if spec_logits is not None:
                     spec_logits[:, spec_steps + 1, :] = current_logp
-        state = self._chain_verify(st, spec_logits)
-        state = state.tolist()
-        n_ok, hit = state[0][0], any(row[1] for row in state)
-        st.stopped = any(row[1] & 2 for row in state)
-        st.double_flag = n_ok == gamma + 1
-        st.count += n_ok - 1
-        st.num += bsz
-        st.emitted += n_ok
-        if st.emitted - 1 + gamma + 2 > output_ids.size(1):
-            return False
-        return not hit
+        emitted = st.emitted
+        go_on = _chain_round_host(st, self._chain_verify(st, spec_logits))
+        st.double_flag = st.emitted - emitted == gamma + 1      # every draft token was accepted
+        return go_on
 
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
@@ -694,17 +754,11 @@ class LlamaGlide(LlamaForCausalLM):
         rules = self._rules(input_ids.device, None, None, sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop,
                             ban=ban, guide=guide)
         self._clear_shard()
-        bsz = input_ids.size(0)
+        bsz, P = input_ids.size(0), int(input_ids.size(1))
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
-        dev = input_ids.device
         self.set_max_gen_len(max_gen_len + (128 if branches == 1 else 256))     # (a tree pass appends up to 80 rows)
-        P = int(input_ids.size(1))
-        self._set_hints(P, P)
-        hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
         input_len = prompt_length
-        rows = torch.arange(bsz, device=dev)
-        logits = self.lm_head(hidden_states[rows, input_len - 1, :])
-        cache_lens = input_ids.new_zeros((bsz)).int() + input_len.int()
+        logits, cache_lens = self._prefill_target(input_ids, input_len)
         first = rules.first_token(logits, input_len, input_ids)
         st = self.begin_lookup_decode(first, cache_lens, input_len, P, input_ids, gamma, max_ngram, min_ngram, max_gen_len, eos_id,
                                       branches=branches, rules=rules)
@@ -739,26 +793,14 @@ class LlamaGlide(LlamaForCausalLM):
             return self._begin_lookup_tree(first_token, cache_lens, input_len, int(prompt_bound), prompt_ids, gamma, branches,
                                            max_ngram, min_ngram, max_gen_len, eos_id, rules)
         st = _DecodeState(gamma=gamma, max_ngram=max_ngram, min_ngram=min_ngram, bsz=bsz, P=int(prompt_bound),
-                          max_gen_len=max_gen_len, count=0, num=0, emitted=1, rounds=0)
+                          max_gen_len=max_gen_len, rounds=0)
         st.prompt_ids = prompt_ids.to(device=dev, dtype=torch.int64)
         if st.prompt_ids.stride(-1) != 1:
             st.prompt_ids = st.prompt_ids.contiguous()
-        st.output_ids = first_token.new_zeros((bsz, max_gen_len + gamma))
-        st.spec_mask = first_token.new_zeros((bsz, max_gen_len + gamma))
-        st.output_ids[:, 0] = first_token
-        st.cache_lens = cache_lens
-        st.input_len = input_len
-        st.input_len_i32 = input_len.to(device=dev, dtype=torch.int32).view(bsz).contiguous()
-        st.spec_buffer = st.output_ids.new_zeros((bsz, gamma + 1))
-        st.spec_buffer[:, 0] = st.output_ids[:, 0]
-        # what chain_commit keeps for a drafter with a cache of its own: scratch here
-        st.draft_cache_lens = cache_lens.clone()
-        st.next_spec_start_token = st.output_ids.new_zeros((bsz, 2))
         st.info = torch.zeros((bsz, 2), dtype=torch.int32, device=dev)
         st.hist = torch.zeros((bsz, max_ngram + 1), dtype=torch.int64, device=dev)
         st.last_lookup = SimpleNamespace(hist=st.hist, info=st.info)
-        st.eos = self._stop_id(eos_id, "spec")
-        rules.bind(st, first_token, prompt_ids, input_len, (st.cache_lens, st.input_len_i32, 1, 0), gamma=gamma)
+        self._chain_state(st, first_token, cache_lens, input_len, eos_id, prompt_ids, rules)
         st.use_graphs = bool(dev.type == "cuda" and bsz == 1 and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
         P, rows = st.P, gamma + 2                          # (the replayer holds no reference to the state that holds it)
         st.replayer = GraphReplayer(self, lambda bound: (P + bound + rows, P + bound + rows), st.output_ids.size(1), "lookup round")
@@ -809,36 +851,17 @@ class LlamaGlide(LlamaForCausalLM):
             return False
         if getattr(st, "branches", 1) > 1:
             return self._lookup_tree_round(st)
-        gamma, bsz = st.gamma, st.bsz
         state = None
         if st.use_graphs and st.rounds >= self.GRAPH_AFTER:
-            rp, device_round = st.replayer, partial(self._lookup_device, st)
-            done = False
-            with rp.guard():
-                rp.roll_over(st.emitted)
-                if rp.captured(None):
-                    state = rp.replay(None)
-                else:
-                    state = rp.warm(None, device_round)               # the warm-up round is this call's round
-                    rp.capture(None, device_round)
-                done = True
-            if not done:
+            state = st.replayer.run(None, partial(self._lookup_device, st), st.emitted, same_call=True)
+            if st.replayer.failed:
                 st.use_graphs = False
-                state = rp.result if rp.issued else None              # a warm-up round that was issued IS the round
         if state is None:
-            bound = st.P + st.emitted + gamma + 2
+            bound = st.P + st.emitted + st.gamma + 2
             self._set_hints(bound, bound)
             state = self._lookup_device(st)
         st.rounds += 1
-        state = state.tolist()                                        # the round's ONE host read
-        n_ok, hit = state[0][0], any(row[1] for row in state)
-        st.stopped = any(row[1] & 2 for row in state)
-        st.count += n_ok - 1
-        st.num += bsz
-        st.emitted += n_ok
-        if st.emitted - 1 + gamma + 2 > st.output_ids.size(1):
-            return False
-        return not hit
+        return _chain_round_host(st, state)
 
     def _begin_lookup_tree(self, first_token, cache_lens, input_len, P: int, prompt_ids, gamma, branches, max_ngram, min_ngram,
                            max_gen_len, eos_id, rules):
@@ -854,39 +877,31 @@ class LlamaGlide(LlamaForCausalLM):
         R = Fn - 1 + gamma + 1
         width = max_gen_len + gamma + 1
         st = _DecodeState(gamma=gamma, branches=branches, max_ngram=max_ngram, min_ngram=min_ngram, Fn=Fn, R=R, P=P, dev=dev,
-                          bsz=bsz, max_gen_len=max_gen_len, rounds=0)
+                          bsz=bsz, max_gen_len=max_gen_len, rounds=0, num=0)
         st.prompt_ids = prompt_ids.to(device=dev, dtype=torch.int64)
         if st.prompt_ids.stride(-1) != 1:
             st.prompt_ids = st.prompt_ids.contiguous()
         st.input_len = input_len
         st.input_len_i32 = input_len.to(device=dev, dtype=torch.int32).view(bsz).contiguous()
-        st.fill = self._tree_output_fill(eos_id)
-        st.output_ids = torch.full((bsz, width), st.fill, dtype=torch.int64, device=dev)
-        st.spec_mask = torch.zeros((bsz, width), dtype=torch.int64, device=dev)
-        st.output_ids[:, 0] = first_token
-        st.cache_lens = cache_lens.to(torch.int32).clone()     # the tree operators advance it in place
-        st.count, st.num = 0, 0
-        st.all_spec = torch.zeros((bsz, Fn), dtype=torch.int64, device=dev)
-        st.all_spec[:, 0] = first_token
-        st.tree_mask = torch.zeros((bsz, Fn, Fn), dtype=torch.int64, device=dev)
-        st.tree_mask[:, :, 0] = 1
-        st.history_logp_sum = torch.zeros((bsz, Fn), dtype=torch.float32, device=dev)   # (tree_commit resets it with the rest)
-        st.acc_pad = torch.zeros((bsz, gamma + 1), dtype=torch.int64, device=dev)
-        st.acc_pad[:, 0] = first_token
-        st.acc_ids = st.acc_pad[:, :1]
-        st.a = 1                              # host mirror of acc_num
-        st.emitted = 1                        # host mirror of emitted_dev: columns of output_ids written so far
-        st.emitted_dev = torch.ones((bsz,), dtype=torch.int32, device=dev)
         st.info = torch.zeros((bsz, branches, 2), dtype=torch.int32, device=dev)
         st.hist = torch.zeros((bsz, max_ngram + 1), dtype=torch.int64, device=dev)
         st.hist_nb = torch.zeros((bsz, branches + 1), dtype=torch.int64, device=dev)
         st.won = torch.zeros((bsz, branches), dtype=torch.int64, device=dev)
         st.last_lookup = SimpleNamespace(hist=st.hist, info=st.info, branches=branches, hist_nb=st.hist_nb, won=st.won)
-        st.eos = self._stop_id(eos_id, "tree")
-        rules.bind(st, first_token, prompt_ids, input_len, (st.emitted_dev, None, 0, st.fill))
+        self._tree_state(st, first_token, cache_lens, input_len, width, eos_id, prompt_ids, rules)
         st.use_graphs = bool(dev.type == "cuda" and bsz == 1 and self.model.layers[-1].self_attn.shard is None and self.GRAPH_ROUNDS)
         st.replayer = GraphReplayer(self, lambda bound: (P + bound + R, P + bound + R), width, "lookup tree round")
         return st
+
+    def _tree_verify_pass(self, st, a: int, **bump):
+        """The V step of a tree-shaped round (:1078-1091), device work only: one R-row target pass over [a accepted | Fn - 1
+        tree nodes | pads].  ``bump`` / ``bump_add``: a length that ``tree_verify_inputs`` advances in its launch.  Returns
+        (the hidden states of rows a-1 .. a+Fn-2, position_ids)."""
+        veri_spec, position_ids, mask_bits = self.ops.tree_verify_inputs(st.acc_pad[:, :a], a, st.all_spec, st.tree_mask,
+                                                                         st.cache_lens, st.R, **bump)
+        hidden_states = self.model.forward(veri_spec, position_ids=position_ids, cache_lens=st.cache_lens,
+                                           exec_type="tree_decoding", tree_mask_bits=mask_bits).last_hidden_state
+        return hidden_states[:, a - 1:a + st.Fn - 1], position_ids
 
     def _tree_accept(self, st, a: int, llm_logits, position_ids, collapse, commit, pred=None):
         """The accept half of a tree-shaped round (``_round_device``, ``_lookup_tree_device``), device work only, from the
@@ -917,19 +932,13 @@ class LlamaGlide(LlamaForCausalLM):
         """The device work of one lookup round with ``branches >= 2`` (no host read inside; ``a``, the tokens the last round
         accepted, is its only host-side parameter): the tree from the text, then the V and A halves of ``_round_device``
         without a draft cache to keep.  Returns state [bsz, 2] = (acc_num, EOS hit | 2 * stop hit)."""
-        Fn, gamma, R, B = st.Fn, st.gamma, st.R, st.branches
-        tree_mask, all_spec = st.tree_mask, st.all_spec
-        ops = self.ops
-        acc_ids = st.acc_pad[:, :a]
+        gamma, B = st.gamma, st.branches
         bound = self.model.layers[-1].self_attn.kv_len_hint or st.P + st.output_ids.size(1)
-        ops.ngram_tree_draft(st.prompt_ids, st.input_len_i32, st.output_ids, st.emitted_dev, bound, gamma, B, st.max_ngram,
-                             st.min_ngram, all_spec, tree_mask, info=st.info, hist=st.hist, hist_nb=st.hist_nb)
-        # ---- V: one R-row target pass over [a accepted | Fn - 1 tree nodes | pads]
-        veri_spec, position_ids, mask_bits = ops.tree_verify_inputs(acc_ids, a, all_spec, tree_mask, st.cache_lens, R)
-        hidden_states = self.model.forward(veri_spec, position_ids=position_ids, cache_lens=st.cache_lens,
-                                           exec_type="tree_decoding", tree_mask_bits=mask_bits).last_hidden_state
+        self.ops.ngram_tree_draft(st.prompt_ids, st.input_len_i32, st.output_ids, st.emitted_dev, bound, gamma, B, st.max_ngram,
+                                  st.min_ngram, st.all_spec, st.tree_mask, info=st.info, hist=st.hist, hist_nb=st.hist_nb)
+        hidden_states, position_ids = self._tree_verify_pass(st, a)                       # ---- V
         # ---- A: the deepest branch that verifies; no KV row moves (the next pass feeds the accepted tokens again)
-        state, acc_num_t, index_mapping = self._tree_accept(st, a, self.lm_head(hidden_states[:, a - 1:a + Fn - 1]), position_ids,
+        state, acc_num_t, index_mapping = self._tree_accept(st, a, self.lm_head(hidden_states), position_ids,
                                                             (st.cache_lens, 1 + B * (gamma - 1), gamma + 1), {})
         # the branch of the deepest accepted node (node = 1 + (d-1) * B + j), where a draft token was accepted at all
         n = acc_num_t.view(-1, 1).to(torch.int64)
@@ -943,23 +952,13 @@ class LlamaGlide(LlamaForCausalLM):
         a = st.a
         state = None
         if st.use_graphs and not st.replayer.disabled and st.rounds >= self.GRAPH_AFTER:
-            state = self._replay_round(st, a, partial(self._lookup_tree_device, st, a))
+            state = st.replayer.run(a, partial(self._lookup_tree_device, st, a), st.emitted)
         if state is None:
             bound = st.P + st.emitted + st.R
             self._set_hints(bound, bound)
             state = self._lookup_tree_device(st, a)
         st.rounds += 1
-        state = state.tolist()                                        # the round's ONE host read
-        a, hit = state[0][0], any(row[1] for row in state)
-        st.stopped = any(row[1] & 2 for row in state)
-        st.acc_ids = st.acc_pad[:, :a]
-        st.a = a
-        st.emitted += a
-        st.count += a - 1
-        st.num += st.bsz
-        if st.emitted + st.gamma + 2 > st.output_ids.size(1):
-            return False
-        return not hit
+        return _tree_round_host(st, state)
 
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
@@ -981,9 +980,6 @@ class LlamaGlide(LlamaForCausalLM):
         self.glide.set_max_gen_len(max_gen_len + 256)
         P = int(input_ids.size(1))
         input_len = prompt_length
-        rows = torch.arange(bsz, device=dev)
-        lens = input_len.to(device=dev, dtype=torch.int32).view(bsz)
-        position_ids = torch.arange(0, input_ids.size(1), device=dev)[None, :]
         for layer in self.model.layers:                    # a model object may be reused with and without a shard
             layer.self_attn.shard = shard
         self.glide.cross_attn.shard = shard
@@ -992,17 +988,12 @@ class LlamaGlide(LlamaForCausalLM):
                 # a mailbox slot holds the record of the widest pass: 128 rows x heads x (128 + 1) floats
                 heads = max(self.config.num_attention_heads, self.glide.config.num_attention_heads)
                 shard.enable_peer_exchange(bsz * 128 * heads * 129, dev)
-            first = self._sharded_prefill(input_ids, input_len, position_ids, shard, rules)
+            lens = input_len.to(device=dev, dtype=torch.int32).view(bsz)
+            first = self._sharded_prefill(input_ids, input_len, shard, rules)
         else:
-            # prefill LLM (:954-960)
-            self._set_hints(P, P)
-            hidden_states = self.model.forward(input_ids, exec_type="prefill").last_hidden_state
-            first = rules.first_token(self.lm_head(hidden_states[rows, input_len - 1, ...]), input_len, input_ids)
-            # prefill glide (:968-975)
-            hidden_states = self.model.embed_tokens(input_ids)
-            position_embeddings = self.model.rotary_emb(hidden_states, position_ids)
-            self.glide(hidden_states=hidden_states, position_embeddings=position_embeddings, llm_kv=self._last_kv(),
-                       cache_lens=lens.clone(), llm_kv_len=lens.clone(), exec_type="prefill")
+            logits, lens = self._prefill_target(input_ids, input_len)
+            first = rules.first_token(logits, input_len, input_ids)
+            self._prefill_draft(input_ids, lens)
         st = self.begin_tree_decode(first, lens, P, tree_shape, max_gen_len, eos_id, temperature=temperature, prompt_ids=input_ids,
                                     rules=rules)
         self.last_logprobs = st.logprobs
@@ -1023,7 +1014,7 @@ class LlamaGlide(LlamaForCausalLM):
             shard.raise_if_exchange_failed()
         return st.output_ids, st.count, st.num, elapsed_time, st.spec_mask
 
-    def _sharded_prefill(self, input_ids, input_len, position_ids, shard, rules):
+    def _sharded_prefill(self, input_ids, input_len, shard, rules):
         """Sequence-sharded prefill: rank r runs the target model on prompt rows [r*Ls, (r+1)*Ls) only
         (one all-gather of the layer's K/V rows per layer, ``LlamaAttention.sharded_prefill``) and keeps that slice of the
         KV; the tail rank computes the first token (``rules.first_token``: under ``logprobs`` its log-prob rows too) and broadcasts it.  The
@@ -1041,8 +1032,8 @@ class LlamaGlide(LlamaForCausalLM):
         shard.prefill_ctx = (lo, hi - lo, P)
         try:
             self._set_hints(P, P)
-            hidden_states = self.model.forward(input_ids[:, lo:hi], position_ids=position_ids[:, lo:hi],
-                                               exec_type="prefill").last_hidden_state
+            hidden_states = self.model.forward(input_ids[:, lo:hi], exec_type="prefill",
+                                               position_ids=torch.arange(lo, hi, device=input_ids.device)[None, :]).last_hidden_state
         finally:
             shard.prefill_ctx = None
         dev = input_ids.device
@@ -1057,8 +1048,7 @@ class LlamaGlide(LlamaForCausalLM):
         for t in rules.first_logprobs or ():
             if t.numel():
                 shard.broadcast_from_tail(t)
-        hidden_states = self.model.embed_tokens(input_ids)
-        self.glide.prefill_cache_only(hidden_states, self.model.rotary_emb(hidden_states, position_ids))
+        self._prefill_draft(input_ids, None)
         return first
 
     def begin_tree_decode(self, first_token, cache_lens, prompt_bound: int, tree_shape=None, max_gen_len=64, eos_id=151645,
@@ -1087,25 +1077,11 @@ class LlamaGlide(LlamaForCausalLM):
         gamma = len(cand)
         R = Fn - 1 + gamma + 1               # verification rows: [a accepted | F-1 tree | pads]
         self._head_of_draft_passes()                    # the draft passes' head and its pack exist before the first warm-up round
-        st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz)
-        st.output_ids = torch.full((bsz, max_gen_len), self._tree_output_fill(eos_id), dtype=torch.int64, device=dev)  # :937 (G8)
-        st.spec_mask = torch.zeros((bsz, max_gen_len), dtype=torch.int64, device=dev)
-        st.output_ids[:, 0] = first_token
+        st = _DecodeState(cand=cand, acc_n=acc_n, Fn=Fn, gamma=gamma, R=R, P=prompt_bound, dev=dev, bsz=bsz, num=bsz)
         cache_lens = cache_lens.to(torch.int32)              # the tree operators advance the three lengths in place
-        st.cache_lens = cache_lens.clone()
+        self._tree_state(st, first_token, cache_lens, cache_lens, max_gen_len, eos_id, prompt_ids, rules)
         st.target_cache_lens_for_draft = cache_lens.clone()
         st.draft_cache_lens = cache_lens.clone()
-        st.count, st.num = 0, bsz
-        st.all_spec = torch.zeros((bsz, Fn), dtype=torch.int64, device=dev)
-        st.all_spec[:, 0] = first_token
-        st.acc_pad = torch.zeros((bsz, gamma + 1), dtype=torch.int64, device=dev)     # accepted ids of the last round
-        st.acc_pad[:, 0] = first_token
-        st.acc_ids = st.acc_pad[:, :1]
-        st.a = 1                              # host mirror of acc_num (G9: the pad id is outside the vocab)
-        st.emitted = 1                        # tokens written to output_ids so far (host mirror of emitted_dev)
-        st.emitted_dev = torch.ones((bsz,), dtype=torch.int32, device=dev)
-        st.fill = self._tree_output_fill(eos_id)
-        rules.bind(st, first_token, prompt_ids, cache_lens, (st.emitted_dev, None, 0, st.fill))
         # HIP graphs of the round, one per `a`: on a GPU; under a KV shard only when its exchange is the peer-store one
         # (kernel launches only: dist.PeerExchange) -- callers that bracket kernels with events switch it off per round
         sh = self.model.layers[-1].self_attn.shard
@@ -1116,10 +1092,6 @@ class LlamaGlide(LlamaForCausalLM):
         P = prompt_bound                                       # (the replayer holds no reference to the state that holds it)
         st.replayer = GraphReplayer(self, lambda bound: (P + bound + R, P + bound + Fn), max_gen_len, "decode round",
                                     bound=self._tier_bound(1, max_gen_len), tiers=1, share_pool=True)
-        st.tree_mask = torch.zeros((bsz, Fn, Fn), dtype=torch.int64, device=dev)
-        st.tree_mask[:, :, 0] = 1
-        st.history_logp_sum = torch.zeros((bsz, Fn), dtype=torch.float32, device=dev)
-        st.eos = self._stop_id(eos_id, "tree")
         st.arange_g = torch.arange(gamma + 2, device=dev)[None, :]
         st.temperature = float(temperature)
         if temperature > 0:
@@ -1150,24 +1122,12 @@ class LlamaGlide(LlamaForCausalLM):
         a = st.a
         state = None
         if st.use_graphs and not st.replayer.disabled and (st.graphs_forced or st.num >= self.GRAPH_AFTER * st.bsz):
-            state = self._graph_round(st, a)
+            state = st.replayer.run(a, partial(self._round_device, st, a), st.emitted)
         if state is None:
             # host bounds: no cache holds more than P + emitted (+ this round's speculative rows) valid rows
             self._set_hints(st.P + st.emitted + st.R, st.P + st.emitted + st.Fn)
             state = self._round_device(st, a)
-        state = state.tolist()                                        # the round's ONE host read
-        a, hit = state[0][0], any(row[1] for row in state)
-        st.stopped = any(row[1] & 2 for row in state)                 # ops.stop_scan raised bit 1
-        st.acc_ids = st.acc_pad[:, :a]
-        st.a = a
-        st.emitted += a
-        st.count += a - 1
-        st.num += st.bsz
-        if st.emitted + st.gamma + 2 > st.output_ids.size(1):         # :1118
-            return False
-        if hit:                                                       # :1120
-            return False
-        return True
+        return _tree_round_host(st, state)
 
     def _tier_bound(self, emitted: int, total: int) -> int:
         """Emitted-token bound of the graph tier that holds `emitted` (GRAPH_TIER; the whole budget when tiers are off)."""
@@ -1175,24 +1135,6 @@ class LlamaGlide(LlamaForCausalLM):
         if not tier or tier <= 0:
             return total
         return min(total, (emitted // tier + 1) * tier)
-
-    def _graph_round(self, st, a: int):
-        """Replay the HIP graph of a round that starts from ``a`` accepted tokens; the first round with a new ``a``
-        runs eagerly on the capture stream (warm-up), the second one is captured.  Returns the round's state tensor, or
-        None when the round has still to run, eagerly."""
-        return self._replay_round(st, a, partial(self._round_device, st, a))
-
-    def _replay_round(self, st, key, device_round):
-        """Warm-up, capture or replay of ``device_round`` under ``key`` (``_graph_round``, ``_graph_round_stochastic``)."""
-        rp = st.replayer
-        with rp.guard():
-            rp.roll_over(st.emitted)
-            if key not in rp.entries:
-                return rp.warm(key, device_round)
-            if not rp.captured(key):
-                rp.capture(key, device_round)
-            return rp.replay(key)
-        return rp.result if rp.issued else None       # a warm-up round that was issued IS the round: never run it twice
 
     def prepare_tree_graphs(self, st):
         """Capture the round graphs of every accepted-token count now instead of on first use (benchmarks: keeps the
@@ -1225,11 +1167,10 @@ class LlamaGlide(LlamaForCausalLM):
         The length tensors are passed without the reference's ``.clone()``: their in-place updates (inside
         ``ops.tree_grow`` / ``tree_verify_inputs`` / ``tree_commit``) are ordered behind the kernels that read them on
         the same stream."""
-        cand, acc_n, Fn, gamma, R, bsz = st.cand, st.acc_n, st.Fn, st.gamma, st.R, st.bsz
+        cand, acc_n, Fn, gamma, bsz = st.cand, st.acc_n, st.Fn, st.gamma, st.bsz
         tree_mask, all_spec, history_logp_sum = st.tree_mask, st.all_spec, st.history_logp_sum
         ops = self.ops
         last_attn = self.model.layers[-1].self_attn
-        acc_ids = st.acc_pad[:, :a]
         # ---- D0: the a accepted tokens through the draft layer (:1003-1027).  At temperature > 0 the reference feeds the
         # whole zero-padded acc_ids row (its width, not acc_num, :1003): the extra rows only write cache rows that are
         # overwritten before they are read, but the ROW COUNT enters the bottom-right alignment of the causal cross-attention
@@ -1286,11 +1227,7 @@ class LlamaGlide(LlamaForCausalLM):
             position_ids, mask_bits = ops.tree_grow(tree_mask, all_spec, history_logp_sum, topk_logp_sum, topk_indices,
                                                     vocab_size, lo, mid, base=st.draft_cache_lens, want_next=ms + 1 < gamma)
         # ---- V: one R-row target pass (:1078-1091); `draft_cache_lens += 1` (:1076) rides in the input assembly
-        veri_spec, position_ids, mask_bits = ops.tree_verify_inputs(acc_ids, a, all_spec, tree_mask, st.cache_lens, R,
-                                                                    bump=st.draft_cache_lens, bump_add=1)
-        hidden_states = self.model.forward(veri_spec, position_ids=position_ids, cache_lens=st.cache_lens,
-                                           exec_type="tree_decoding", tree_mask_bits=mask_bits).last_hidden_state
-        hidden_states = hidden_states[:, a - 1:a + Fn - 1]
+        hidden_states, position_ids = self._tree_verify_pass(st, a, bump=st.draft_cache_lens, bump_add=1)
         if st.temperature > 0:
             return self.lm_head(hidden_states)         # the stochastic branch continues in tree_round_stochastic
         # under a shard with `vocab_parallel` every rank takes the arg-max over its slice of the lm_head: no row of logits to rule
@@ -1399,7 +1336,7 @@ class LlamaGlide(LlamaForCausalLM):
         st.mt_words.copy_(st.mt_host, non_blocking=True)       # (the round's host read below is behind this copy)
         st.noise.copy_(noise.view(1, V))
         device_round = partial(self._stochastic_device, st, a)
-        state = self._replay_round(st, (a, st.d0_rows), device_round)
+        state = st.replayer.run((a, st.d0_rows), device_round, st.emitted)
         if state is None:                              # the capture failed before the round was issued: eagerly, same draws
             bound = min(st.emitted, st.output_ids.size(1))
             self._set_hints(st.P + bound + st.R, st.P + bound + st.Fn)

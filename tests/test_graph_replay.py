@@ -1,4 +1,5 @@
-"""The HIP-graph state machine of `vanilla_step` / `tree_round` / `prepare_tree_graphs` (longspec_amd/graphs.py) without a GPU.
+"""The HIP-graph state machine of `vanilla_step` / `tree_round` / `prepare_tree_graphs` / `lookup_round` (longspec_amd/graphs.py)
+without a GPU.
 
 The CUDA primitives the graph code touches are replaced by recording fakes: a fake capture stores the device-function calls made
 inside it WITHOUT running them (a stream capture records, it does not execute), a fake `replay` runs them again on the live decode
@@ -16,12 +17,14 @@ import pytest
 import torch
 
 import cases
+import lookup_oracle
+import lookup_tree_oracle
 import oracle_ops
 
 
-def build(run):
+def build(run, ops=oracle_ops):
     from longspec_amd.llama_glide import LlamaGlide
-    m = LlamaGlide(run["cfg"], ops=oracle_ops, dtype=run.get("dtype", torch.float16))
+    m = LlamaGlide(run["cfg"], ops=ops, dtype=run.get("dtype", torch.float16))
     m.load_state_dict({**run["target_sd"], **{"glide." + k: v for k, v in run["draft_sd"].items()}}, strict=True)
     return m
 
@@ -213,7 +216,43 @@ def run_vanilla(fk, run, tier_fails=False):
     return dict(out=out, num=int(num), vs=states[0], steps=calls["vanilla_step"])
 
 
+def run_lookup(fk, run, branches, tier_fails=False):
+    """lookup_generate of a golden run through the real loop (branches=1: the chain round, 3: the tree round), graphs forced on
+    behind begin_lookup_decode."""
+    m = build(run, ops=lookup_oracle.ops if branches == 1 else lookup_tree_oracle.ops)
+    m.GRAPH_AFTER, m.GRAPH_TIER = 0, TIER
+    fk.spy_hints(m)
+    if branches == 1:
+        fk.spy_device(m, "_lookup_device", lambda st: "round")
+    else:
+        fk.spy_device(m, "_lookup_tree_device", lambda st, a: a)
+    calls, states, begin = {}, [], m.begin_lookup_decode
+    _count_calls(m, "lookup_round", calls)
+
+    def begin_with_graphs(*a, **k):
+        st = begin(*a, **k)
+        st.use_graphs = True
+        states.append(st)
+        if tier_fails:
+            m._tier_bound = _boom
+        return st
+
+    m.begin_lookup_decode = begin_with_graphs
+    out, count, num, _, _ = m.lookup_generate(run["prompt"], torch.tensor([run["prompt_len"]]), gamma=4, max_ngram=3, min_ngram=1,
+                                              max_gen_len=run["max_gen_len"], eos_id=run["eos_id"], branches=branches)
+    return dict(out=out, count=int(count), num=int(num), st=states[0], rounds=calls["lookup_round"])
+
+
+LOOKUP_BRANCHES = {"lookup": 1, "lookup_tree": 3}
 SCENARIOS = [(name, kind) for name in RUNS for kind in ("tree", "tree_prepared", "vanilla")]
+SCENARIOS += [(name, kind) for name in RUNS for kind in LOOKUP_BRANCHES]      # (behind the others: the trace file's key order)
+
+
+def _check_lookup_text(r, run):
+    """The text is the vanilla text over the columns the loop wrote (the vanilla golden is cut behind its first EOS)."""
+    n = min(r["st"].emitted, run["vanilla_num"] + 1)
+    assert n > 1 and torch.equal(r["out"][:, :n], run["vanilla_out"][:, :n])
+    assert r["num"] == r["rounds"] and r["count"] == r["st"].emitted - 1 - r["rounds"]
 
 
 def scenario(fk, name, kind):
@@ -222,6 +261,9 @@ def scenario(fk, name, kind):
     if kind == "vanilla":
         r = run_vanilla(fk, run)
         return r, {"events": fk.events, "graph_captures": r["vs"].graph_captures}
+    if kind in LOOKUP_BRANCHES:
+        r = run_lookup(fk, run, LOOKUP_BRANCHES[kind])
+        return r, {"events": fk.events, "graph_tiers": r["st"].graph_tiers, "graph_captures": r["st"].graph_captures}
     r = run_tree(fk, run, prepare=kind == "tree_prepared")
     return r, {"events": fk.events, "graph_tiers": r["st"].graph_tiers, "graph_captures": r["st"].graph_captures}
 
@@ -236,6 +278,10 @@ def test_graph_path_issues_the_recorded_trace(fakes, name, kind):
     if kind == "vanilla":
         assert torch.equal(r["out"], run["vanilla_out"]) and r["num"] == run["vanilla_num"]
         assert r["vs"].use_graphs is True and fakes.runs == r["steps"]
+    elif kind in LOOKUP_BRANCHES:
+        _check_lookup_text(r, run)
+        assert r["st"].use_graphs is True and r["st"].graphs is not False and fakes.runs == r["rounds"]
+        assert r["st"].graph_tiers >= 3
     else:
         assert torch.equal(r["out"], run["tree_out"])
         assert (r["count"], r["num"]) == (run["tree_count"], run["tree_num"])
@@ -296,14 +342,34 @@ def test_vanilla_step_decodes_every_token_once_when_its_graph_fails(fakes, where
     _check_stream_wait(fakes, where)
 
 
-@pytest.mark.parametrize("loop", [run_tree, run_vanilla], ids=["tree", "vanilla"])
+def _lookup_loop(branches):
+    return lambda fk, run, tier_fails=False: run_lookup(fk, run, branches, tier_fails=tier_fails)
+
+
+@pytest.mark.parametrize("kind", list(LOOKUP_BRANCHES))
+@pytest.mark.parametrize("where", list(FAILURES))
+def test_lookup_round_runs_every_round_once_when_its_graph_fails(fakes, where, kind):
+    """The two failure tests above on the lookup loops.  The chain round switches ``use_graphs`` off as ``vanilla_step`` does;
+    the tree round leaves it to ``replayer.disabled`` as ``tree_round`` does."""
+    run = RUNS["mixed"]
+    r = _run_failing(fakes, _lookup_loop(LOOKUP_BRANCHES[kind]), FAILURES[where])
+    assert fakes.runs == r["rounds"], (fakes.runs, r["rounds"])
+    _check_lookup_text(r, run)
+    assert fakes.events[-1][0] == "eager"
+    assert r["st"].replayer.disabled is True and r["st"].graphs is False
+    assert r["st"].use_graphs is (kind == "lookup_tree")
+    _check_stream_wait(fakes, where)
+
+
+@pytest.mark.parametrize("loop", [run_tree, run_vanilla, _lookup_loop(1), _lookup_loop(3)],
+                         ids=["tree", "vanilla", "lookup", "lookup_tree"])
 def test_a_failure_inside_a_capture_propagates(fakes, loop):
     """While the stream is capturing nothing can run eagerly: the exception is the caller's."""
     fakes.fail, fakes.stuck_capturing = {"capture": 1}, True
     with warnings.catch_warnings():
         warnings.simplefilter("error")
         with pytest.raises(RuntimeError, match="injected: capture 1 failed"):
-            loop(fakes, RUNS["gqa_mixed"])
+            loop(fakes, RUNS["gqa_mixed" if loop in (run_tree, run_vanilla) else "mixed"])
 
 
 def test_the_eager_loops_give_the_goldens_the_failure_tests_compare_with():
