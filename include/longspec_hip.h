@@ -510,6 +510,37 @@ int ls_ban_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t str
                 const int32_t* base_sub, int base_add, const int64_t* extra_ids, int64_t ids_stride_b, const int64_t* extra_mask,
                 int64_t mask_stride_b, int64_t mask_stride_r, int n_extra, void* stream);
 
+/* The DRY repetition penalty on the target's logits (dry=; csrc/dry.hip; no counterpart in the reference).
+ * table: int32 [LS_DRY_TABLE_WORDS] on the device -- [0] number of breakers (0..64), [1] allowed_length (1..LS_DRY_MAX_MATCH),
+ * [2] last_n (0 = the whole text, else 1..2^23), [3] the word count, [4:37] pen[0 .. 32] as fp32 bits, [37:101] the breaker ids
+ * (-1 padded).  Counts are clamped to this layout on the device before they index anything.
+ *
+ * ls_dry_rows: 16-bit logits [b, rows, vocab] (strides in elements, unit column stride, rows must not overlap), IN PLACE, two
+ * launches of one kernel.  The text t of row (z, r), its m tokens, w, output_ids, base / base_sub / base_add and the extras are
+ * those of ls_ban_rows, n_extra 0..LS_BAN_MAX_EXTRA included.  With lo = max(0, m - last_n) (last_n = 0: 0): nothing changes if
+ * m - lo < 2 or t[m-1] is a breaker.  For every j in [lo, m-2] with t[j] == t[m-1], L(j) is the largest L <= LS_DRY_MAX_MATCH
+ * with j-k >= lo, t[j-k] == t[m-1-k] and t[j-k] no breaker for all k < L; len[v] = the maximum of L(j) over the j with
+ * t[j+1] == v.  Every v inside [0, vocab) with len[v] >= allowed_length becomes dtype(float(logits[z, r, v]) - pen[len[v]]): one
+ * fp32 subtract, rounded to nearest even; a NaN keeps its bits, -inf stays -inf.  Every other element keeps its bits; ids
+ * outside [0, vocab) take part in the matches (compared as 64-bit integers) and are never penalised.
+ * scratch: int32, scratch_words >= b * rows * vocab, indexed [z, r, v] densely; ALL ZERO ON ENTRY, ALL ZERO ON EXIT.  Pass 0 raises
+ * scratch[z, r, v] to len[v] with device-scope atomic maxima, pass 1 visits the same positions and the one thread whose
+ * compare-and-swap (len[v] -> 0) succeeds rewrites the element: one writer per element, bits that do not depend on scheduling, a
+ * scratch that cleans itself.  The cost depends on the text, never on vocab: no sweep of the scratch or of the rows.
+ * Grid (ceil(rows / 4) + ceil(width / LS_BAN_CHUNK) * ceil(rows / 32), b) workgroups of 256, twice: a path workgroup takes one row
+ * per wave and the positions j >= w-1, whose candidate t[j+1] is a token of the row's path; a chunk workgroup reads the columns
+ * [k * LS_BAN_CHUNK - 32, (k + 1) * LS_BAN_CHUNK] once into LDS and tests its positions j <= w-2 against the last 32 tokens of
+ * each of its 32 rows (a chunk at or behind w-1, or in front of every row's lo: it returns at once).  The grid depends on
+ * host-side shapes only: nothing is read back, nothing is allocated, safe inside a replayed graph.
+ * LS_ERR_INVALID_ARG, before any launch: the refusals of ls_ban_rows, table_words != LS_DRY_TABLE_WORDS, a null or misaligned
+ * scratch or scratch_words < b * rows * vocab. */
+#define LS_DRY_MAX_MATCH 32
+#define LS_DRY_TABLE_WORDS 101
+int ls_dry_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t stride_b, int64_t stride_r, const int32_t* table,
+                int table_words, const int64_t* output_ids, int64_t out_stride_b, int width, int32_t* scratch, int64_t scratch_words,
+                const int32_t* base, const int32_t* base_sub, int base_add, const int64_t* extra_ids, int64_t ids_stride_b,
+                const int64_t* extra_mask, int64_t mask_stride_b, int64_t mask_stride_r, int n_extra, void* stream);
+
 /* Guided decoding: a deterministic automaton over token ids on the target's logits (guide=; csrc/guide.hip; no counterpart in
  * the reference).  table: int32 [table_words] on the device, 16-byte aligned (longspec_amd/guide.py builds it) --
  *   [0] S >= 1   [1] C (1..LS_GUIDE_MAX_CLASSES)   [2] start   [3] vocab   [4] the word count   [5:8] reserved (0)

@@ -12,4 +12,5 @@ from .logprobs import Logprobs  # noqa: E402,F401
 from .stop import Stop  # noqa: E402,F401
 from .ban import Ban  # noqa: E402,F401
 from .guide import Guide  # noqa: E402,F401
+from .dry import Dry  # noqa: E402,F401
 from . import regex  # noqa: E402,F401

@@ -1,5 +1,5 @@
-"""What the six request keywords of the decode loops (``sampling=``, ``penalties=``, ``logprobs=``, ``stop=``, ``ban=``,
-``guide=``) have in common: how an argument and the process-wide default become the object a loop runs with."""
+"""What the request keywords of the decode loops (``sampling=``, ``penalties=``, ``logprobs=``, ``stop=``, ``ban=``,
+``guide=``, ``dry=``) have in common: how an argument and the process-wide default become the object a loop runs with."""
 from __future__ import annotations
 
 

@@ -23,6 +23,8 @@ One function per reference seam of the draft-then-verify round:
   stop_scan / stop_ban_rows   stop tokens, stop sequences and min_tokens (stop=; no counterpart)
   ban_rows               banned sequences and no-repeat n-grams on the target's logits, per row from the committed text and the
                          row's ordered path (ban=; no counterpart)
+  dry_rows               the DRY repetition penalty on the target's logits: an id loses the more the longer the repeat it would
+                         extend, per row from the committed text and the row's ordered path (dry=; no counterpart)
   guide_rows / guide_advance   guided decoding: the tokens a DFA over token ids forbids in the state behind the row's path, and
                          the per-row committed state they start from (guide=; no counterpart)
   guide_lift (_hash / _cols / _check)   the classes of a vocabulary's tokens under a byte-level DFA, the set-up of a guide
@@ -745,6 +747,42 @@ def ban_rows(logits: torch.Tensor, table: torch.Tensor, output_ids: Optional[tor
     _C.check(_C.load().ls_ban_rows(x.data_ptr(), b, R, V, _dtype(x), x.stride(0), max(x.stride(1), V), table.data_ptr(),
                                    BAN_TABLE_WORDS, out_p, out_sb, W, _len_i32(base, b, "base"), _len_i32(base_sub, b, "base_sub"),
                                    int(base_add), ids_p, ids_sb, mask_p, mask_sb, mask_sr, C, _stream()), "ls_ban_rows")
+    return logits
+
+
+DRY_TABLE_WORDS = 101      # int32 words of a dry table (longspec_amd/dry.py, LS_DRY_TABLE_WORDS)
+DRY_MAX_MATCH = 32         # the depth matches are measured to (LS_DRY_MAX_MATCH)
+
+
+def dry_rows(logits: torch.Tensor, table: torch.Tensor, output_ids: Optional[torch.Tensor], scratch: torch.Tensor,
+             base: Optional[torch.Tensor] = None, base_sub: Optional[torch.Tensor] = None, base_add: int = 0,
+             extra_ids: Optional[torch.Tensor] = None, extra_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The DRY repetition penalty on TARGET logits [b, V] or [b, R, V] (16-bit, unit column stride, any non-overlapping row
+    strides), IN PLACE (``ls_dry_rows``, two launches of one kernel; the definition is ``longspec_amd/dry.py``).  The text of a
+    row -- ``output_ids``, ``base`` / ``base_sub`` / ``base_add``, ``extra_ids`` / ``extra_mask`` -- is that of ``ban_rows``.
+    Every id whose emission would extend a repeat of at least ``allowed_length`` tokens loses ``pen[length]`` of ``table``
+    (``Dry.table``); every other element keeps its bits.  ``scratch``: a contiguous int32 tensor of at least b * R * V
+    elements that the CALLER owns, all zero on entry and all zero again on exit; nothing is allocated and nothing is read
+    back.  Returns ``logits``."""
+    _dev(logits, table, output_ids, scratch, base, base_sub, extra_ids, extra_mask)
+    x, b, R, V = _rule_rows(logits, "dry_rows")
+    if table.dtype != torch.int32 or table.dim() != 1 or table.numel() != DRY_TABLE_WORDS or not table.is_contiguous():
+        raise TypeError(f"dry_rows: table must be a contiguous int32 [{DRY_TABLE_WORDS}] tensor (Dry.table)")
+    if scratch.dtype != torch.int32 or not scratch.is_contiguous() or scratch.numel() < b * R * V:
+        raise TypeError(f"dry_rows: scratch must be a contiguous int32 tensor of at least b * R * V = {b * R * V} elements")
+    out_p, out_sb, W = None, 0, 0
+    if output_ids is not None:
+        if output_ids.dtype != torch.int64 or output_ids.dim() != 2 or output_ids.shape[0] != b or output_ids.stride(1) != 1:
+            raise TypeError(f"dry_rows: output_ids must be int64 [{b}, W] with contiguous rows")
+        W = output_ids.shape[1]
+        if b > 1 and output_ids.stride(0) < W:
+            raise ValueError("dry_rows: output_ids rows must be at least W elements apart")
+        out_p, out_sb = (output_ids.data_ptr(), max(output_ids.stride(0), W)) if W else (None, 0)
+    ids_p, ids_sb, mask_p, mask_sb, mask_sr, C = _extras(extra_ids, extra_mask, b, R, "dry_rows", BAN_MAX_EXTRA)
+    _C.check(_C.load().ls_dry_rows(x.data_ptr(), b, R, V, _dtype(x), x.stride(0), max(x.stride(1), V), table.data_ptr(),
+                                   DRY_TABLE_WORDS, out_p, out_sb, W, scratch.data_ptr(), scratch.numel(),
+                                   _len_i32(base, b, "base"), _len_i32(base_sub, b, "base_sub"), int(base_add), ids_p, ids_sb,
+                                   mask_p, mask_sb, mask_sr, C, _stream()), "ls_dry_rows")
     return logits
 
 
