@@ -541,6 +541,48 @@ int ls_dry_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t str
                 const int32_t* base, const int32_t* base_sub, int base_add, const int64_t* extra_ids, int64_t ids_stride_b,
                 const int64_t* extra_mask, int64_t mask_stride_b, int64_t mask_stride_r, int n_extra, void* stream);
 
+/* Watermarked decoding: a keyed green-list bias on the target's logits, and its detector (watermark=; csrc/watermark.hip; no
+ * counterpart in the reference).  This definition is a public contract: a text marked today verifies with a later build.
+ * All arithmetic is on unsigned 64-bit words, modulo 2^64, with M1 = 0x9E3779B97F4A7C15, M2 = 0xBF58476D1CE4E5B9,
+ * M3 = 0x94D049BB133111EB:
+ *   fin(z):  z = (z ^ (z >> 30)) * M2;  z = (z ^ (z >> 27)) * M3;  return z ^ (z >> 31)        (the SplitMix64 finaliser)
+ *   state of the context c_1 .. c_h, oldest first (int64 ids reinterpreted as uint64, whatever their value):
+ *            s = fin(key + M1);  for each c_i:  s = fin((s ^ c_i) + M1)
+ *   u(s, v) = fin(s + (v + 1) * M1);  v is GREEN after that context iff (u >> 32) < T.
+ * table: int32 [LS_WATERMARK_TABLE_WORDS] on the device -- [0] h (1..LS_WATERMARK_MAX_CONTEXT; clamped on the device), [1] T =
+ * floor(gamma * 2^32) as bits (1..2^32-1), [2] delta as fp32 bits, [3] the word count, [4] [5] the key's low and high word,
+ * [6] [7] zero.
+ *
+ * ls_watermark_rows: 16-bit logits [b, rows, vocab] (strides in elements, unit column stride, rows must not overlap), IN PLACE,
+ * one launch.  The text t of row (z, r), its m tokens, w, output_ids, base / base_sub / base_add and the extras are those of
+ * ls_ban_rows, n_extra 0..LS_BAN_MAX_EXTRA included.  A row with m < h keeps its bits and its elements are not read.  Otherwise
+ * s is the state of t[m-h .. m-1] and every green v inside [0, vocab) becomes dtype(float(logits[z, r, v]) + delta): one fp32
+ * add, rounded to nearest even; a NaN keeps its bits, -inf stays -inf.  Every element that is not green keeps its bits.  NOT
+ * idempotent: a second call adds delta again.  Grid (ceil((vocab + 7) / 8192), rows, b) workgroups of 256: wave 0 assembles the
+ * row's path in LDS, takes the last h tokens from the path's tail and -- where the path is shorter -- from the end of the
+ * committed columns, folds them serially and leaves s in LDS; every thread then takes four groups of eight ids that are
+ * 16-byte aligned in memory -- one 16-byte load, the eight u by additions of M1 from one multiplied-out start, and one 16-byte
+ * store unless none of the eight is green --; the groups that hang over a row's two ends (a row is only 2-byte aligned, vocab
+ * may be odd) go element by element.  Nothing is allocated, nothing is read back: safe inside a replayed graph.
+ * LS_ERR_INVALID_ARG, before any launch: the refusals of ls_ban_rows, with table_words != LS_WATERMARK_TABLE_WORDS.
+ *
+ * ls_watermark_score: ids int64 [b, n] (row stride stride_b >= n; n 0..2^31-1), lengths int32 [b] or NULL (clamped to 0..n;
+ * NULL: n).  Position c of row z is scored iff h <= c < length; it is green iff ids[z, c] is green after ids[z, c-h .. c-1].
+ * counts int32 [b, 2] = (scored, green), OVERWRITTEN (cleared on the stream in front of the launch, then integer atomic adds of
+ * per-workgroup ballot counts: the result does not depend on scheduling); flags int8 [b, n] dense or NULL: -1 not scored,
+ * 0 red, 1 green; hashes uint64 [b, n] dense or NULL: u of a scored position, 0 elsewhere.  Grid (ceil(n / 256), b) workgroups
+ * of 256, a thread per position, which folds its own context; n = 0: the counts are cleared and nothing is launched.
+ * LS_ERR_INVALID_ARG: a null table / counts / ids, table_words, b outside 1..65535, n out of range, stride_b < n with b > 1,
+ * misaligned counts or hashes. */
+#define LS_WATERMARK_TABLE_WORDS 8
+#define LS_WATERMARK_MAX_CONTEXT 8
+int ls_watermark_rows(void* logits, int b, int rows, int vocab, int dtype, int64_t stride_b, int64_t stride_r, const int32_t* table,
+                      int table_words, const int64_t* output_ids, int64_t out_stride_b, int width, const int32_t* base,
+                      const int32_t* base_sub, int base_add, const int64_t* extra_ids, int64_t ids_stride_b, const int64_t* extra_mask,
+                      int64_t mask_stride_b, int64_t mask_stride_r, int n_extra, void* stream);
+int ls_watermark_score(const int64_t* ids, int b, int64_t n, int64_t stride_b, const int32_t* lengths, const int32_t* table,
+                       int table_words, int32_t* counts, int8_t* flags, uint64_t* hashes, void* stream);
+
 /* Guided decoding: a deterministic automaton over token ids on the target's logits (guide=; csrc/guide.hip; no counterpart in
  * the reference).  table: int32 [table_words] on the device, 16-byte aligned (longspec_amd/guide.py builds it) --
  *   [0] S >= 1   [1] C (1..LS_GUIDE_MAX_CLASSES)   [2] start   [3] vocab   [4] the word count   [5:8] reserved (0)

@@ -117,6 +117,8 @@ SYMBOLS = {
     "ls_stop_ban_rows": (C.c_int, [_P, _I, _I, _I, _I, _L, _L, _P, _I, _P, _P, _I, _I, _P, _L, _L, _I, _P]),
     "ls_ban_rows": (C.c_int, [_P, _I, _I, _I, _I, _L, _L, _P, _I, _P, _L, _I, _P, _P, _I, _P, _L, _P, _L, _L, _I, _P]),
     "ls_dry_rows": (C.c_int, [_P, _I, _I, _I, _I, _L, _L, _P, _I, _P, _L, _I, _P, _L, _P, _P, _I, _P, _L, _P, _L, _L, _I, _P]),
+    "ls_watermark_rows": (C.c_int, [_P, _I, _I, _I, _I, _L, _L, _P, _I, _P, _L, _I, _P, _P, _I, _P, _L, _P, _L, _L, _I, _P]),
+    "ls_watermark_score": (C.c_int, [_P, _I, _L, _L, _P, _P, _I, _P, _P, _P, _P]),
     "ls_guide_rows": (C.c_int, [_P, _I, _I, _I, _I, _L, _L, _P, _I, _P, _P, _L, _P, _L, _L, _I, _P]),
     "ls_guide_advance": (C.c_int, [_P, _I, _P, _I, _P, _I, _L, _P, _L, _P]),
     "ls_guide_lift_hash": (C.c_int, [_P, _P, _P, _L, _I, _I, _P, _P, _P]),

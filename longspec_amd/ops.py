@@ -42,6 +42,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import math
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import torch
@@ -784,6 +785,68 @@ def dry_rows(logits: torch.Tensor, table: torch.Tensor, output_ids: Optional[tor
                                    _len_i32(base, b, "base"), _len_i32(base_sub, b, "base_sub"), int(base_add), ids_p, ids_sb,
                                    mask_p, mask_sb, mask_sr, C, _stream()), "ls_dry_rows")
     return logits
+
+
+WATERMARK_TABLE_WORDS = 8  # int32 words of a watermark table (longspec_amd/watermark.py, LS_WATERMARK_TABLE_WORDS)
+WATERMARK_MAX_CONTEXT = 8  # the tokens that key a position's green list, at the most (LS_WATERMARK_MAX_CONTEXT)
+
+
+def _watermark_table(table: torch.Tensor, who: str):
+    if table.dtype != torch.int32 or table.dim() != 1 or table.numel() != WATERMARK_TABLE_WORDS or not table.is_contiguous():
+        raise TypeError(f"{who}: table must be a contiguous int32 [{WATERMARK_TABLE_WORDS}] tensor (Watermark.table)")
+
+
+def watermark_rows(logits: torch.Tensor, table: torch.Tensor, output_ids: Optional[torch.Tensor], base: Optional[torch.Tensor] = None,
+                   base_sub: Optional[torch.Tensor] = None, base_add: int = 0, extra_ids: Optional[torch.Tensor] = None,
+                   extra_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The keyed green-list bias on TARGET logits [b, V] or [b, R, V] (16-bit, unit column stride, any non-overlapping row
+    strides), IN PLACE (``ls_watermark_rows``, one launch; the definition is ``longspec_amd/watermark.py``).  The text of a row
+    -- ``output_ids``, ``base`` / ``base_sub`` / ``base_add``, ``extra_ids`` / ``extra_mask`` -- is that of ``ban_rows``.  Every
+    id that is green after the row's last ``h`` tokens gains ``delta`` of ``table`` (``Watermark.table``); a row of fewer than
+    ``h`` tokens and every other element keep their bits.  Not idempotent: a second call adds ``delta`` again.  Nothing is
+    allocated and nothing is read back.  Returns ``logits``."""
+    _dev(logits, table, output_ids, base, base_sub, extra_ids, extra_mask)
+    x, b, R, V = _rule_rows(logits, "watermark_rows")
+    _watermark_table(table, "watermark_rows")
+    out_p, out_sb, W = None, 0, 0
+    if output_ids is not None:
+        if output_ids.dtype != torch.int64 or output_ids.dim() != 2 or output_ids.shape[0] != b or output_ids.stride(1) != 1:
+            raise TypeError(f"watermark_rows: output_ids must be int64 [{b}, W] with contiguous rows")
+        W = output_ids.shape[1]
+        if b > 1 and output_ids.stride(0) < W:
+            raise ValueError("watermark_rows: output_ids rows must be at least W elements apart")
+        out_p, out_sb = (output_ids.data_ptr(), max(output_ids.stride(0), W)) if W else (None, 0)
+    ids_p, ids_sb, mask_p, mask_sb, mask_sr, C = _extras(extra_ids, extra_mask, b, R, "watermark_rows", BAN_MAX_EXTRA)
+    _C.check(_C.load().ls_watermark_rows(x.data_ptr(), b, R, V, _dtype(x), x.stride(0), max(x.stride(1), V), table.data_ptr(),
+                                         WATERMARK_TABLE_WORDS, out_p, out_sb, W, _len_i32(base, b, "base"),
+                                         _len_i32(base_sub, b, "base_sub"), int(base_add), ids_p, ids_sb, mask_p, mask_sb, mask_sr, C,
+                                         _stream()), "ls_watermark_rows")
+    return logits
+
+
+def watermark_score(ids: torch.Tensor, table: torch.Tensor, lengths: Optional[torch.Tensor] = None, want_flags: bool = True,
+                    want_hashes: bool = False):
+    """The watermark detector's counts for token ids int64 [n] or [b, n] (unit column stride, rows at least n apart)
+    (``ls_watermark_score``, one launch; the definition is ``longspec_amd/watermark.py``).  ``lengths``: int32 [b] on the
+    device or None, row z is ``ids[z, :lengths[z]]`` (clamped to 0..n).  Returns a namespace of ``counts`` int32 [b, 2] --
+    scored and green positions --, ``flags`` int8 [b, n] (-1 not scored, 0 red, 1 green; None without ``want_flags``) and
+    ``hashes`` uint64 [b, n] (``u`` of a scored position, 0 elsewhere; None without ``want_hashes``).  Nothing is read back."""
+    _dev(ids, table, lengths)
+    if ids.dtype != torch.int64 or ids.dim() not in (1, 2):
+        raise TypeError("watermark_score: ids must be int64 [n] or [b, n]")
+    x = ids if ids.dim() == 2 else ids.unsqueeze(0)
+    b, n = x.shape
+    if n > 0 and (x.stride(1) != 1 or (b > 1 and x.stride(0) < n)):
+        raise ValueError("watermark_score: ids must have unit column stride and rows at least n elements apart")
+    _watermark_table(table, "watermark_score")
+    counts = torch.empty((b, 2), dtype=torch.int32, device=x.device)
+    flags = torch.empty((b, n), dtype=torch.int8, device=x.device) if want_flags else None
+    hashes = torch.empty((b, n), dtype=torch.uint64, device=x.device) if want_hashes else None
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    _C.check(_C.load().ls_watermark_score(ptr(x), b, n, max(x.stride(0), n) if n else 0, _len_i32(lengths, b, "lengths"),
+                                          table.data_ptr(), WATERMARK_TABLE_WORDS, counts.data_ptr(), ptr(flags), ptr(hashes),
+                                          _stream()), "ls_watermark_score")
+    return SimpleNamespace(counts=counts, flags=flags, hashes=hashes)
 
 
 GUIDE_HEADER_WORDS = 8     # int32 words in front of a guide table's class area (longspec_amd/guide.py, LS_GUIDE_HEADER_WORDS)

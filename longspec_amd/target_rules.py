@@ -1,11 +1,12 @@
 """The rules on the TARGET's logits, in one place: what ``sampling=``, ``penalties=``, ``logprobs=``, ``stop=``, ``ban=``,
-``guide=`` and ``dry=`` of the generate loops and the ``begin_*_decode`` entry points (``llama_glide.py``) do to a row of target logits, and
+``guide=``, ``dry=`` and ``watermark=`` of the generate loops and the ``begin_*_decode`` entry points (``llama_glide.py``) do to a
+row of target logits, and
 the state they keep.  The loops build one ``TargetRules`` before any prefill and call it instead of spelling the operators out;
 a new rule is added here and nowhere else.  The draft passes are never ruled: the drafter stays greedy, unpenalised, unbanned
-and unguided (no DRY penalty either), so a rule changes the acceptance length, never what the target accepts.
+and unguided (no DRY penalty and no watermark either), so a rule changes the acceptance length, never what the target accepts.
 
 The keywords (each: the argument, else -- where no ``temperature`` is given or it is 0 -- the process-wide default
-LONGSPEC_SAMPLING / _PENALTIES / _LOGPROBS / _STOP / _BAN / _GUIDE / _DRY, else off; all refused at ``temperature > 0``, the
+LONGSPEC_SAMPLING / _PENALTIES / _LOGPROBS / _STOP / _BAN / _GUIDE / _DRY / _WATERMARK, else off; all refused at ``temperature > 0``, the
 reference's own T > 0 path):
 
 * ``sampling`` (``sampling.py``): every token of the target is one draw from its filtered distribution instead of the arg-max,
@@ -29,10 +30,12 @@ reference's own T > 0 path):
   tokens loses the more the longer that repeat is.  No state beyond the text; ``dry.scratch`` is the operator's int32 work
   area [bsz, R, V], all zero between calls, grown (never inside a graph capture: the warm-up round in front of a capture has
   the capture's shapes) to the largest pass seen.
+* ``watermark`` (``watermark.py``): every id that a keyed hash of the last ``context`` tokens of the text so far plus the row's
+  draft tokens calls green gains ``delta``; a row with fewer tokens than that keeps its bits.  No state beyond the text.
 * ``logprobs`` (``logprobs.py``): the log-prob of every emitted token under the ruled distribution it was taken from and its
   top-n alternatives, in ``token`` [bsz, W] / ``top_ids`` / ``top`` [bsz, W, top_n], column for column with ``output_ids``.
 
-Order inside a round: penalties, dry, ``min_tokens`` ban, ban, guide (``apply``); arg-max or draw (``tokens``); log-prob rows
+Order inside a round: penalties, dry, watermark, ``min_tokens`` ban, ban, guide (``apply``); arg-max or draw (``tokens``); log-prob rows
 (``pending``); then behind the loop's own commit ``record`` (``logprob_commit``) and ``advance`` (``token_state_add``,
 ``guide_advance``, the stop scan -- last: it erases log-prob columns ``record`` wrote).  A rule that is off fetches no operator.
 
@@ -56,6 +59,7 @@ from .logprobs import new_buffers as _logprob_buffers, resolve as _resolve_logpr
 from .penalties import resolve as _resolve_penalties
 from .sampling import resolve as _resolve_sampling
 from .stop import new_state as _stop_state, resolve as _resolve_stop, result_of as _stop_result
+from .watermark import resolve as _resolve_watermark
 
 
 class TargetRules:
@@ -64,7 +68,7 @@ class TargetRules:
     the shard's ``head_select`` (the tree loop), so ``sampling`` is refused under a vocabulary-parallel shard too."""
 
     def __init__(self, ops, vocab: int, device, temperature=None, shard=None, head_sharded=False, sampling=None, penalties=None,
-                 logprobs=None, stop=None, ban=None, guide=None, dry=None):
+                 logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None):
         self.ops, self.vocab, self.device = ops, vocab, device
         self.sampling = _resolve_sampling(sampling, temperature, use_env=True)
         self.penalties = _resolve_penalties(penalties, temperature, use_env=True)
@@ -73,16 +77,17 @@ class TargetRules:
         ban = _resolve_ban(ban, temperature, use_env=True)
         guide = _resolve_guide(guide, temperature, use_env=True)
         dry = _resolve_dry(dry, temperature, use_env=True)
+        watermark = _resolve_watermark(watermark, temperature, use_env=True)
         if shard is not None and shard.vocab_parallel:
             for name, on in (("stop= with min_tokens > 0", stop is not None and stop.min_tokens > 0),
                              ("sampling=", head_sharded and self.sampling is not None), ("penalties=", self.penalties is not None),
                              ("logprobs=", lpc is not None), ("ban=", ban is not None), ("guide=", guide is not None),
-                             ("dry=", dry is not None)):
+                             ("dry=", dry is not None), ("watermark=", watermark is not None)):
                 if on:
                     raise ValueError(f"{name} is not available with a vocabulary-parallel shard")
         # (the tables check the ids, and nothing is copied to the device inside a graph capture)
         self.bias_table = self.penalties.bias_table(vocab, device) if self.penalties is not None else None
-        self.stop = self.ban = self.guide = self.dry = None
+        self.stop = self.ban = self.guide = self.dry = self.watermark = None
         if stop is not None:
             self.stop = SimpleNamespace(cfg=stop, table=stop.table(vocab, device), min_tokens=stop.min_tokens)
         if ban is not None:
@@ -91,6 +96,8 @@ class TargetRules:
             self.guide = SimpleNamespace(cfg=guide, table=guide.table(vocab, device), state=None)
         if dry is not None:
             self.dry = SimpleNamespace(cfg=dry, table=dry.table(vocab, device), scratch=None, retired=[])
+        if watermark is not None:
+            self.watermark = SimpleNamespace(cfg=watermark, table=watermark.table(vocab, device))
         self.top_n = lpc.top_n if lpc is not None else None
         self.lp_temperature = self.sampling.temperature if self.sampling is not None else 1.0     # the sampler's; 1: greedy
         # until bind(): the text is empty (the first token's row)
@@ -137,7 +144,8 @@ class TargetRules:
         """Attach to the decode state ``st`` (``st.output_ids`` with the first token in place, and ``st.spec_mask`` where the
         loop has one, exist): sets ``st.rules`` and the attributes callers read -- ``sampling``, ``penalties``,
         ``token_state``, ``bias_table``, ``logprobs``, ``stop``, ``stop_state``, ``last_stop``, ``stopped``, ``ban``,
-        ``guide``, ``dry`` --, counts ``first_token`` [bsz] into the penalty and guide states, writes ``first_logprobs`` to column 0
+        ``guide``, ``dry``, ``watermark`` --, counts ``first_token`` [bsz] into the penalty and guide states, writes ``first_logprobs``
+        to column 0
         (None, a caller that starts from synthetic caches: column 0 keeps the fill) and tests column 0 against the stops (a
         hit ends the loop with its first round, without a host read here).  ``where``: see the module; ``gamma``: the draft
         length of a chain-shaped round, whose verification row i follows the draft tokens ``spec_buffer[:, 1 : i + 1]``."""
@@ -150,7 +158,7 @@ class TargetRules:
             self.streams = torch.arange(bsz, device=dev, dtype=torch.int32)
             self.arange_v = torch.arange(gamma + 1, device=dev)[None, :] if gamma is not None else None
         if gamma is not None and (self.penalties is not None or self.ban is not None or self.guide is not None
-                                  or self.dry is not None):
+                                  or self.dry is not None or self.watermark is not None):
             self.chain_mask = torch.ones((gamma + 1, gamma), dtype=torch.int64, device=dev).tril(-1)
         if self.top_n is not None:
             lp = _logprob_buffers(bsz, width, self.top_n, dev)
@@ -164,7 +172,7 @@ class TargetRules:
             self.last_stop = _stop_result(self.stop_state)
         st.rules, st.stopped = self, False
         for name in ("sampling", "penalties", "token_state", "bias_table", "logprobs", "stop", "stop_state", "last_stop", "ban",
-                     "guide", "dry"):
+                     "guide", "dry", "watermark"):
             setattr(st, name, getattr(self, name))
         self.advance(first_token.to(device=dev, dtype=torch.int64).view(bsz, 1))
 
@@ -190,6 +198,8 @@ class TargetRules:
                 self.dry.scratch = torch.zeros((need,), dtype=torch.int32, device=logits.device)
             logits = ops.dry_rows(logits, self.dry.table, self.text, self.dry.scratch, extra_ids=extra_ids, extra_mask=extra_mask,
                                   **where)
+        if self.watermark is not None:
+            logits = ops.watermark_rows(logits, self.watermark.table, self.text, extra_ids=extra_ids, extra_mask=extra_mask, **where)
         if self.stop is not None and self.stop.min_tokens > 0:
             logits = ops.stop_ban_rows(logits, self.stop.table, depth=depth, tree_mask=tree_mask, **where)
         if self.ban is not None:
