@@ -390,6 +390,37 @@ typedef struct ls_sample_desc {
 size_t ls_sample_ex_workspace_bytes(const ls_sample_desc* d);
 int ls_sample_rows_ex(const ls_sample_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ls_sample_rows_ex with two cuts (csrc/sample_cut.hip; longspec_amd/cut.py).  Order: top_n_sigma -> top_k -> top_p -> min_p ->
+ * typical_p -> xtc, each on the set the former kept.  m is the row maximum, T the temperature of the descriptor.
+ *   top_n_sigma = n, finite and >= 0 (0 = off): over the N finite logits of the row (-inf takes no part) sigma =
+ *     sqrt(sum (x - mean)^2 / N), the population deviation of the raw 16-bit values, NOT divided by T; keep x_j >= m - n sigma.
+ *     A threshold set that holds the maximum, so it intersects with top_k in either order, and top_p's mass is taken over what
+ *     both kept.  sigma = 0 (one finite logit, all equal) keeps the maxima; a row without a finite logit is left alone.  The
+ *     sums are taken in double on y = x - m in a fixed order (per-chunk partial records, plain stores, summed in chunk order):
+ *     the bits do not depend on scheduling.
+ *   xtc = (probability P in [0, 1], 0 = off; threshold theta in (0, 1]), "exclude top choices".  The row's coin is
+ *     Philox4x32-10 with key (seed lo, seed hi) and counter (0xFFFFFFFF, position lo, position hi, stream) -- token noise has
+ *     counter word 0 = column >> 2 < 2^22, the streams cannot meet --, u = ((w0 >> 9) + 0.5) * 2^-23, and the cut happens iff
+ *     u < P in fp32.  Then, with S the set kept so far, F(v) = floor(2^40 exp((v - m) / T)) in double as top_p forms it and
+ *     Z = sum of F over S (unsigned 64-bit): v* = the smallest value occurring in S with F(v*) >= ceil(theta Z), and every j in S
+ *     with x_j > v* is dropped.  ALL tokens tied at v* stay (llama.cpp keeps one of them; the rule mirrors top_k's ties).  If
+ *     only the largest value of S qualifies, or none does, the row is unchanged: theta > 0.5 is a no-op without a tie at the
+ *     top.  One departure from the letter of the rule: where Z = 0 -- typical_p has moved S more than 40 ln 2 * T below m, so
+ *     that every F floors to 0 -- ceil(theta * 0) = 0 would let every value qualify; such a row is left unchanged.  A row whose
+ *     coin does not fire is not read by the xtc kernels.
+ * out_kept, out_threshold, out_upper and the top-2 outputs describe the final set.  With `cut` NULL or both filters off the
+ * launches and every output bit are those of ls_sample_rows_ex.
+ * LS_ERR_INVALID_ARG, before any launch: as ls_sample_rows_ex, and top_n_sigma < 0 or not finite, xtc_probability outside
+ * [0, 1], xtc_threshold outside (0, 1], a NaN in any of them, reserved != 0. */
+typedef struct ls_sample_cut {
+    float top_n_sigma, xtc_probability, xtc_threshold;
+    int32_t reserved;            /* 0 */
+} ls_sample_cut;
+
+/* Scratch for ls_sample_rows_cut: that of ls_sample_rows_ex (the cuts keep their partial records in its histogram area). */
+size_t ls_sample_cut_workspace_bytes(const ls_sample_desc* d, const ls_sample_cut* cut);
+int ls_sample_rows_cut(const ls_sample_desc* d, const ls_sample_cut* cut, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Token penalties and a logit bias on TARGET logits, in front of ls_argmax_rows / ls_sample_rows (csrc/penalty.hip; no counterpart
  * in the reference).  state [b, vocab] int32 (batch stride state_stride_b): bits 0-30 of a word = times the token was generated
  * (first token included), bit 31 = the token occurs in the valid part of the prompt.  logits / out [b, rows, vocab] dtype with

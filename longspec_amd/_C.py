@@ -66,6 +66,11 @@ class SampleDesc(C.Structure):
     ]
 
 
+class SampleCut(C.Structure):
+    """Mirror of ``ls_sample_cut`` (include/longspec_hip.h) -- keep field order in sync."""
+    _fields_ = [("top_n_sigma", C.c_float), ("xtc_probability", C.c_float), ("xtc_threshold", C.c_float), ("reserved", C.c_int32)]
+
+
 # every symbol include/longspec_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int
@@ -107,6 +112,8 @@ SYMBOLS = {
                                  _P]),
     "ls_sample_ex_workspace_bytes": (C.c_size_t, [C.POINTER(SampleDesc)]),
     "ls_sample_rows_ex": (C.c_int, [C.POINTER(SampleDesc), _P, C.c_size_t, _P]),
+    "ls_sample_cut_workspace_bytes": (C.c_size_t, [C.POINTER(SampleDesc), C.POINTER(SampleCut)]),
+    "ls_sample_rows_cut": (C.c_int, [C.POINTER(SampleDesc), C.POINTER(SampleCut), _P, C.c_size_t, _P]),
     "ls_penalize_rows": (C.c_int, [_P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _P, _L, _P, _L, _P, _L, _L, _I, C.c_float, C.c_float,
                                    C.c_float, _P, _P]),
     "ls_token_state_add": (C.c_int, [_P, _I, _I, _L, _P, _I, _L, _P, _L, _I, _P]),

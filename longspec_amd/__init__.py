@@ -14,4 +14,5 @@ from .ban import Ban  # noqa: E402,F401
 from .guide import Guide  # noqa: E402,F401
 from .dry import Dry  # noqa: E402,F401
 from .watermark import Watermark  # noqa: E402,F401
+from .cut import Cut  # noqa: E402,F401
 from . import regex  # noqa: E402,F401

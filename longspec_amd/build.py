@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(LIBDIR, "liblongspec_hip.so")
 SOURCES = ["attn.hip", "ban.hip", "dry.hip", "gemm.hip", "gemm_w8.hip", "gemm_w4.hip", "guide.hip", "guide_lift.hip", "logprob.hip", "lookup.hip", "lookup_tree.hip", "misc.hip", "penalty.hip",
-           "sample.hip", "sample_band.hip", "stop.hip", "topk.hip", "tree.hip", "watermark.hip", "xgmi.hip"]
+           "sample.hip", "sample_band.hip", "sample_cut.hip", "stop.hip", "topk.hip", "tree.hip", "watermark.hip", "xgmi.hip"]
 HEADERS = [os.path.join(CSRC, "ls_common.h"), os.path.join(CSRC, "skinny_gemm.h"), os.path.join(CSRC, "lookup_text.h"),
            os.path.join(CSRC, "sample_common.h"), os.path.join(CSRC, "rule_rows.h"),
            os.path.join(os.path.dirname(HERE), "include", "longspec_hip.h")]

@@ -25,6 +25,10 @@
 // ls_sample_rows_ex adds min_p (one more lower bound) and typical_p (a band [lower, upper] of values that may exclude the
 // maximum): their kernels are in sample_band.hip and run between the selections above and the key pass, which honours
 // `upper` as well as `lower` and reports the largest kept value.  With both off the launches are the ones listed here.
+//
+// ls_sample_rows_cut adds top_n_sigma (a lower bound from the raw logits, behind the top-k levels and in front of the top-p
+// levels) and xtc (an upper bound on the rows whose coin fires, last in front of the key pass): sample_cut.hip.  With both off,
+// again, the launches are the ones listed here.
 #include "sample_common.h"
 
 namespace {
@@ -273,8 +277,10 @@ SampleWs sample_ws(int rows, int vocab) {
     return w;
 }
 
-// Both entry points: d.min_p = 0 and d.typical_p = 1 issue the launches of ls_sample_rows and nothing else.
-int sample_run(const ls_sample_desc& d, void* workspace, size_t workspace_bytes, void* stream, const char* who) {
+// All three entry points: d.min_p = 0 and d.typical_p = 1 issue the launches of ls_sample_rows and nothing else, and so does a
+// `cut` that is NULL or has both of its filters off.
+int sample_run(const ls_sample_desc& d, const ls_sample_cut* cut, void* workspace, size_t workspace_bytes, void* stream,
+               const char* who) {
     const void* logits = d.logits;
     const int rows = d.rows, vocab = d.vocab, dtype = d.dtype, top_k = d.top_k;
     const int64_t ld = d.ld;
@@ -292,9 +298,17 @@ int sample_run(const ls_sample_desc& d, void* workspace, size_t workspace_bytes,
                 (double)d.typical_p);
     if (reinterpret_cast<uintptr_t>(logits) % 16 != 0 || reinterpret_cast<uintptr_t>(workspace) % 16 != 0)
         LS_FAIL(LS_ERR_INVALID_ARG, "%s: logits and workspace must be 16-byte aligned", who);
+    if (cut && (!(cut->top_n_sigma >= 0.f) || !(cut->top_n_sigma < INFINITY) || !(cut->xtc_probability >= 0.f) ||
+                !(cut->xtc_probability <= 1.f) || !(cut->xtc_threshold > 0.f) || !(cut->xtc_threshold <= 1.f) || cut->reserved != 0))
+        LS_FAIL(LS_ERR_INVALID_ARG, "%s: top_n_sigma=%g (finite, >= 0), xtc_probability=%g (0 <= P <= 1), xtc_threshold=%g "
+                "(0 < theta <= 1), reserved=%d (0)", who, (double)cut->top_n_sigma, (double)cut->xtc_probability,
+                (double)cut->xtc_threshold, (int)cut->reserved);
     const SampleWs w = sample_ws(rows, vocab);
     const bool use_k = top_k > 0 && top_k < vocab, use_p = top_p < 1.f, use_m = d.min_p > 0.f, use_t = d.typical_p < 1.f;
+    const bool use_s = cut && cut->top_n_sigma > 0.f, use_x = cut && cut->xtc_probability > 0.f;
     if (workspace_bytes < w.total + (use_t ? ls_sample_band_bytes(rows) : 0)) LS_FAIL(LS_ERR_WORKSPACE, "%s: workspace too small", who);
+    if ((use_s || use_x) && ls_sample_cut_scratch_bytes(rows, vocab) > w.cand - w.hist)      // the cuts' records live in `hist`
+        LS_FAIL(LS_ERR_WORKSPACE, "%s: the histogram area does not hold the partial records of the cuts", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* base = static_cast<char*>(workspace);
     RowState* state = reinterpret_cast<RowState*>(base + w.state);
@@ -317,10 +331,13 @@ int sample_run(const ls_sample_desc& d, void* workspace, size_t workspace_bytes,
         return LS_OK;
     };
     int rc;
-    const int filtered = (use_k || use_p || use_m || use_t) ? 1 : 0;
+    const int filtered = (use_k || use_p || use_m || use_t || use_s || use_x) ? 1 : 0;
+    const unsigned seed_lo = (unsigned)d.seed, seed_hi = (unsigned)(d.seed >> 32);
     if (filtered) {
         if ((rc = hist_pass(0, 0))) return rc;           // also the row maximum, lower = 0 and upper = 0xffff
         if (use_k && (rc = hist_pass(1, 0))) return rc;
+        // (the partial records of the cuts live in `hist`: no pass of this function has it in use across them)
+        if (use_s && (rc = ls_sample_sigma_launch(logits, rows, vocab, (long)ld, dtype, cut->top_n_sigma, state, hist, s))) return rc;
         if (use_p) {
             if ((rc = hist_pass(0, 1))) return rc;
             if ((rc = hist_pass(1, 1))) return rc;
@@ -329,8 +346,10 @@ int sample_run(const ls_sample_desc& d, void* workspace, size_t workspace_bytes,
         if (use_t && (rc = ls_sample_band_launch(logits, rows, vocab, (long)ld, dtype, temperature, d.typical_p, state,
                                                  base + w.total, s)))
             return rc;
+        if (use_x && (rc = ls_sample_xtc_launch(logits, rows, vocab, (long)ld, dtype, temperature, cut->xtc_probability,
+                                                cut->xtc_threshold, d.positions, d.streams, seed_lo, seed_hi, state, hist, s)))
+            return rc;
     }
-    const unsigned seed_lo = (unsigned)d.seed, seed_hi = (unsigned)(d.seed >> 32);
     if (dtype == LS_F16)
         hipLaunchKernelGGL(sample_key_kernel<ElemF16>, grid, block, 0, s, static_cast<const _Float16*>(logits), (long)ld, vocab,
                            d.positions, d.streams, seed_lo, seed_hi, temperature, filtered, state, cand);
@@ -369,12 +388,22 @@ int ls_sample_rows(const void* logits, int rows, int vocab, int64_t ld, int dtyp
     d.ld = ld; d.seed = seed;
     d.rows = rows; d.vocab = vocab; d.dtype = dtype; d.top_k = top_k;
     d.temperature = temperature; d.top_p = top_p; d.min_p = 0.f; d.typical_p = 1.f;
-    return sample_run(d, workspace, workspace_bytes, stream, "ls_sample_rows");
+    return sample_run(d, nullptr, workspace, workspace_bytes, stream, "ls_sample_rows");
 }
 
 int ls_sample_rows_ex(const ls_sample_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
     if (!d) LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows_ex: null descriptor");
-    return sample_run(*d, workspace, workspace_bytes, stream, "ls_sample_rows_ex");
+    return sample_run(*d, nullptr, workspace, workspace_bytes, stream, "ls_sample_rows_ex");
+}
+
+size_t ls_sample_cut_workspace_bytes(const ls_sample_desc* d, const ls_sample_cut* cut) {
+    (void)cut;                                           // the cuts keep their partial records in the histogram area
+    return ls_sample_ex_workspace_bytes(d);
+}
+
+int ls_sample_rows_cut(const ls_sample_desc* d, const ls_sample_cut* cut, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!d) LS_FAIL(LS_ERR_INVALID_ARG, "ls_sample_rows_cut: null descriptor");
+    return sample_run(*d, cut, workspace, workspace_bytes, stream, "ls_sample_rows_cut");
 }
 
 }  // extern "C"

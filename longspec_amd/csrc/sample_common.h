@@ -1,5 +1,6 @@
-// sample_common.h -- what sample.hip (the draw, top-k, top-p) and sample_band.hip (min_p, typical_p) share: the per-row
-// selection state, the ordered 16-bit key, the chunk loader and the Philox of ls_sample_rows / ls_sample_rows_ex.
+// sample_common.h -- what sample.hip (the draw, top-k, top-p), sample_band.hip (min_p, typical_p) and sample_cut.hip
+// (top_n_sigma, xtc) share: the per-row selection state, the ordered 16-bit key, the chunk loader and the Philox of
+// ls_sample_rows / ls_sample_rows_ex / ls_sample_rows_cut.
 #pragma once
 #include "ls_common.h"
 
@@ -12,7 +13,7 @@ struct RowState {
     unsigned long long target;          // what is left of the target inside `bin`
     float m;                            // row maximum
     unsigned upper;                     // ordered 16-bit key: logits above it take no part (0xffff = all)
-    unsigned pad[2];
+    unsigned pad[2];                    // xtc: [0] the cut key (0 = no cut), [1] the smallest occupied key at or above it
 };
 
 __device__ __forceinline__ unsigned order_key(unsigned bits16) {       // as topk.hip: -0.0 and +0.0 share 0x8000
@@ -80,3 +81,14 @@ size_t ls_sample_band_bytes(int rows);                                   // coun
 int ls_sample_minp_launch(int rows, int dtype, float temperature, float min_p, RowState* state, hipStream_t s);
 int ls_sample_band_launch(const void* logits, int rows, int vocab, long ld, int dtype, float temperature, float typical_p,
                           RowState* state, void* band_ws, hipStream_t s);
+
+// sample_cut.hip: the launches of the two cuts of ls_sample_rows_cut.  top_n_sigma runs behind the top-k levels and in front
+// of the top-p levels (lower = max(lower, key of m - n sigma)); xtc runs behind ls_sample_band_launch and in front of the key
+// pass (upper = key of v*, on the rows whose coin fires).  `scratch`: ls_sample_cut_scratch_bytes, rewritten by every call --
+// sample.hip hands over its histogram area, which is free between two of its passes, after checking that it is large enough.
+size_t ls_sample_cut_scratch_bytes(int rows, int vocab);
+int ls_sample_sigma_launch(const void* logits, int rows, int vocab, long ld, int dtype, float n_sigma, RowState* state, void* scratch,
+                           hipStream_t s);
+int ls_sample_xtc_launch(const void* logits, int rows, int vocab, long ld, int dtype, float temperature, float probability,
+                         float threshold, const int64_t* positions, const int32_t* streams, unsigned seed_lo, unsigned seed_hi,
+                         RowState* state, void* scratch, hipStream_t s);

@@ -11,6 +11,32 @@ from contextlib import contextmanager
 
 import torch
 
+_pinned = {}             # device index -> (graph, cell) that pin the generator's capture state, or the exception that kept them from it
+
+
+def _pin_generator_state(stream):
+    """torch creates the capture state of a device's default generator -- two one-element tensors that every capture and every
+    replay fills in place -- at the first capture, and drops it when the last graph dies.  The loops capture inside
+    ``torch.inference_mode``: created there the state is a pair of inference tensors, and a capture or a replay OUTSIDE
+    inference mode (a caller's own graph around an operator, as the operator tests take) fails on that in-place update for as
+    long as one of the loops' graphs is alive -- which the garbage collector decides.  One tiny graph captured outside
+    inference mode in front of a device's first capture here, and kept for the life of the process, pins the state as ordinary
+    tensors, which both modes may update.  Never replayed.  ``stream``: the capture stream of the caller; only a device's real
+    stream has a generator behind it.  Best effort: a failure leaves everything as it was, and the loop's own capture, which
+    follows, reports what it meets."""
+    if not isinstance(stream, torch.Stream) or stream.device_index in _pinned:
+        return
+    _pinned[stream.device_index] = None
+    try:
+        with torch.inference_mode(False), torch.cuda.device(stream.device_index):
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                cell = torch.zeros(1, device="cuda")
+        _pinned[stream.device_index] = (graph, cell)
+    except Exception as e:               # noqa: BLE001
+        _pinned[stream.device_index] = e     # kept for whoever asks why; one warning, the loops go on as before this existed
+        warnings.warn(f"the generator's capture state could not be pinned outside inference mode ({type(e).__name__}: {e})")
+
 
 class GraphReplayer:
     """Entries per key: absent, ``"warm"`` (the device function has run once on the capture stream: the operator layer's
@@ -61,6 +87,7 @@ class GraphReplayer:
 
     def capture(self, key, device_fn):
         self._set_hints()
+        _pin_generator_state(self.stream)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=self.stream, pool=self.pool):
             result = device_fn()

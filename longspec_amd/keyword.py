@@ -1,5 +1,5 @@
 """What the request keywords of the decode loops (``sampling=``, ``penalties=``, ``logprobs=``, ``stop=``, ``ban=``,
-``guide=``, ``dry=``, ``watermark=``) have in common: how an argument and the process-wide default become the object a loop runs with."""
+``guide=``, ``dry=``, ``watermark=``, ``cut=``) have in common: how an argument and the process-wide default become the object a loop runs with."""
 from __future__ import annotations
 
 

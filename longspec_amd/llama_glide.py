@@ -422,7 +422,7 @@ class LlamaGlide(LlamaForCausalLM):
 
     @torch.inference_mode()
     def vanilla_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645, sampling=None,
-                         penalties=None, logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None):                                      # :552-585
+                         penalties=None, logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None, cut=None):                                      # :552-585
         """``sampling`` / ``penalties`` / ``logprobs`` / ``stop`` / ``ban`` / ``guide``: the rules on the target's logits
         (``target_rules.py``), on every step's one row; with ``sampling`` this loop is the denominator of a sampled speculative
         run, and with the same seed the same text.  The log-probs are published as ``self.last_logprobs``, the stop result as
@@ -431,7 +431,7 @@ class LlamaGlide(LlamaForCausalLM):
         last row's stop; the built-in EOS test runs alongside, unchanged."""
         assert input_ids is not None, "please give the input"
         rules = self._rules(input_ids.device, None, None, sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop,
-                            ban=ban, guide=guide, dry=dry, watermark=watermark)
+                            ban=ban, guide=guide, dry=dry, watermark=watermark, cut=cut)
         self._clear_shard()
         bsz, P = input_ids.size(0), int(input_ids.size(1))
         output_ids = input_ids.new_zeros((bsz, max_gen_len))
@@ -490,9 +490,9 @@ class LlamaGlide(LlamaForCausalLM):
 
     # ------------------------------------------------------------------------------------------
     def begin_vanilla_decode(self, output_ids, cache_lens, input_len, prompt_bound: int, sampling=None, penalties=None,
-                             prompt_ids=None, logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None, rules=None):
+                             prompt_ids=None, logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None, cut=None, rules=None):
         """State of the vanilla loop (``llama_glide.py:566-583``): ``output_ids`` [bsz, max_gen] with the first
-        token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32.  The eight keywords:
+        token in place, ``cache_lens`` [bsz] int32 valid rows of every cache, ``input_len`` [bsz] int32.  The nine keywords:
         ``target_rules.py`` (``rules``: the ``TargetRules`` the caller has built from them already, for the first token);
         ``prompt_ids[z, :input_len[z]]`` is the prompt the penalty state starts from (None: no prompt flags).  Every step rules
         its one row, which predicts column ``cache_lens - input_len + 1``.  A row that has stopped keeps decoding with the
@@ -500,7 +500,7 @@ class LlamaGlide(LlamaForCausalLM):
         dev = output_ids.device
         if rules is None:
             rules = self._rules(dev, None, self.model.layers[-1].self_attn.shard, sampling=sampling, penalties=penalties,
-                                logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark)
+                                logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark, cut=cut)
         vs = _DecodeState(output_ids=output_ids, cache_lens=cache_lens, input_len=input_len, P=prompt_bound, step=0,
                           rows=torch.arange(output_ids.size(0), device=dev))
         rules.bind(vs, output_ids[:, 0], prompt_ids, input_len, (cache_lens, input_len, 1, 0))
@@ -541,18 +541,18 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def spec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                      sampling=None, penalties=None, logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None):                          # :621-774
+                      sampling=None, penalties=None, logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None, cut=None):                          # :621-774
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="glide",
-                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark)
+                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark, cut=cut)
 
     @torch.inference_mode()
     def magicdec_generate(self, input_ids, prompt_length, gamma=4, max_gen_len=64, eos_id=151645, temperature=0.0,
-                          sampling=None, penalties=None, logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None):                      # :776-913
+                          sampling=None, penalties=None, logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None, cut=None):                      # :776-913
         """The MagicDec baseline of the reference's harness (``--method magicdec``): chain speculation where the
         drafter is the TARGET itself attending to a StreamingLLM cache (32 sink rows + the last 1024 prompt rows +
         what it generates), verified exactly like ``spec_generate``.  Same return tuple."""
         return self._chain_generate(input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter="magicdec",
-                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark)
+                                    sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark, cut=cut)
 
     @torch.inference_mode()
     def vanilla_torch_generate(self, input_ids, prompt_length, max_gen_len=64, eos_id=151645):                      # :587-619
@@ -563,10 +563,10 @@ class LlamaGlide(LlamaForCausalLM):
         return self.vanilla_generate(input_ids, prompt_length, max_gen_len=max_gen_len, eos_id=eos_id)
 
     def _chain_generate(self, input_ids, prompt_length, gamma, max_gen_len, eos_id, temperature, drafter, sampling=None,
-                        penalties=None, logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None):
+                        penalties=None, logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None, cut=None):
         assert input_ids is not None, "please give the input"
         rules = self._rules(input_ids.device, temperature, None, sampling=sampling, penalties=penalties, logprobs=logprobs,
-                            stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark)
+                            stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark, cut=cut)
         magic = drafter == "magicdec"      # (temperature > 0: the same rejection block in both loops, :715-736 = :854-875)
         self._clear_shard()
         bsz, P = input_ids.size(0), int(input_ids.size(1))
@@ -594,11 +594,11 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_chain_decode(self, first_token, cache_lens, input_len, prompt_bound: int, gamma=4, max_gen_len=64, eos_id=151645,
                            temperature=0.0, drafter="glide", first_logits=None, sampling=None, penalties=None, prompt_ids=None,
-                           logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None, rules=None):
+                           logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None, cut=None, rules=None):
         """State of the chain-speculation loop right after the prefills (``llama_glide.py:641-668``): ``first_token`` [bsz]
         = the target's first generated token, ``cache_lens`` [bsz] int32 = valid rows of every cache (the draft's included),
         ``input_len`` [bsz] = prompt length, ``prompt_bound`` = host-side bound of it.  Also the entry point of benchmarks
-        that time ``chain_round`` on synthetic KV (bench.py --method seq).  The eight keywords: ``target_rules.py`` (``rules``:
+        that time ``chain_round`` on synthetic KV (bench.py --method seq).  The nine keywords: ``target_rules.py`` (``rules``:
         the ``TargetRules`` the caller has built from them already); ``prompt_ids[z, :input_len[z]]`` is the prompt the penalty
         state starts from (None: no prompt flags).  A round rules the gamma + 1 verification rows: row i follows the text so
         far plus the i draft tokens in front of it and predicts column ``cache_lens - input_len + 1 + i``; the rows a round
@@ -607,7 +607,7 @@ class LlamaGlide(LlamaForCausalLM):
         bsz = first_token.size(0)
         if rules is None:
             rules = self._rules(first_token.device, temperature, self.model.layers[-1].self_attn.shard, sampling=sampling,
-                                penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark)
+                                penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark, cut=cut)
         if drafter != "magicdec":
             self._head_of_draft_passes()                # the draft passes' head and its pack exist before the first round
         st = SimpleNamespace(gamma=gamma, magic=drafter == "magicdec", temperature=temperature, bsz=bsz, P=int(prompt_bound),
@@ -731,7 +731,7 @@ class LlamaGlide(LlamaForCausalLM):
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def lookup_generate(self, input_ids, prompt_length, gamma=7, max_ngram=3, min_ngram=1, max_gen_len=64, eos_id=151645,
-                        sampling=None, penalties=None, logprobs=None, stop=None, branches=1, ban=None, guide=None, dry=None, watermark=None):
+                        sampling=None, penalties=None, logprobs=None, stop=None, branches=1, ban=None, guide=None, dry=None, watermark=None, cut=None):
         """Prompt-lookup (n-gram) speculation (no counterpart in the reference): chain speculation whose drafter is the text
         itself -- the ``gamma`` tokens that followed the most recent earlier occurrence of the last ``min_ngram .. max_ngram``
         tokens of prompt + output (``lookup.py``) -- verified exactly like ``spec_generate``.  No draft weights, no draft KV,
@@ -752,7 +752,7 @@ class LlamaGlide(LlamaForCausalLM):
         assert input_ids is not None, "please give the input"
         gamma, max_ngram, min_ngram = _lookup_check(gamma, max_ngram, min_ngram, branches)
         rules = self._rules(input_ids.device, None, None, sampling=sampling, penalties=penalties, logprobs=logprobs, stop=stop,
-                            ban=ban, guide=guide, dry=dry, watermark=watermark)
+                            ban=ban, guide=guide, dry=dry, watermark=watermark, cut=cut)
         self._clear_shard()
         bsz, P = input_ids.size(0), int(input_ids.size(1))
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
@@ -776,7 +776,7 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_lookup_decode(self, first_token, cache_lens, input_len, prompt_bound: int, prompt_ids, gamma=7, max_ngram=3,
                             min_ngram=1, max_gen_len=64, eos_id=151645, sampling=None, penalties=None, logprobs=None, stop=None,
-                            branches=1, ban=None, guide=None, dry=None, watermark=None, rules=None):
+                            branches=1, ban=None, guide=None, dry=None, watermark=None, cut=None, rules=None):
         """State of the prompt-lookup loop right after the target's prefill: the arguments of ``begin_chain_decode`` that have
         a meaning without a drafter, plus ``prompt_ids`` [bsz, P] -- here not optional: ``prompt_ids[z, :input_len[z]]`` is the
         front of the text the drafter searches (and, under ``penalties``, the source of the prompt flags).  Also the entry point
@@ -788,7 +788,7 @@ class LlamaGlide(LlamaForCausalLM):
         dev = first_token.device
         if rules is None:
             rules = self._rules(dev, None, self.model.layers[-1].self_attn.shard, sampling=sampling, penalties=penalties,
-                                logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark)
+                                logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark, cut=cut)
         if branches > 1:
             return self._begin_lookup_tree(first_token, cache_lens, input_len, int(prompt_bound), prompt_ids, gamma, branches,
                                            max_ngram, min_ngram, max_gen_len, eos_id, rules)
@@ -964,15 +964,15 @@ class LlamaGlide(LlamaForCausalLM):
     @torch.inference_mode()
     def tree_spec_generate(self, input_ids, prompt_length, tree_shape: Optional[List[int]] = None, max_gen_len=64,
                            eos_id=151645, temperature=0.0, shard=None, sampling=None, penalties=None,
-                           logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None):                                               # :915-1126
+                           logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None, cut=None):                                               # :915-1126
         """``shard`` (``dist.KVShard``, every rank of the group calls with the same arguments): the prompt is prefilled
         and its KV kept sequence-sharded over the ranks (``_sharded_prefill``); decoding then runs replicated with one
-        exchange per attention call.  Returns the same values on every rank.  The eight keywords: ``target_rules.py``, on every
+        exchange per attention call.  Returns the same values on every rank.  The nine keywords: ``target_rules.py``, on every
         verification row; the log-probs are published as ``self.last_logprobs``, the stop result as ``self.last_stop``.  With
         a ``vocab_parallel`` shard all of them but a ``stop`` without ``min_tokens`` are refused."""
         assert input_ids is not None, "please give the input"
         rules = self._rules(input_ids.device, temperature, shard, head_sharded=True, sampling=sampling, penalties=penalties,
-                            logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark)
+                            logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark, cut=cut)
         bsz = input_ids.size(0)
         assert bsz == 1, "the reference's hot path is batch 1 (SURVEY section 1)"
         dev = input_ids.device
@@ -1053,11 +1053,11 @@ class LlamaGlide(LlamaForCausalLM):
 
     def begin_tree_decode(self, first_token, cache_lens, prompt_bound: int, tree_shape=None, max_gen_len=64, eos_id=151645,
                           temperature=0.0, sampling=None, penalties=None, prompt_ids=None, logprobs=None, stop=None, ban=None,
-                          guide=None, dry=None, watermark=None, rules=None):
+                          guide=None, dry=None, watermark=None, cut=None, rules=None):
         """State of the round loop right after the two prefills (``llama_glide.py:927-991``).
         ``first_token`` [bsz] = the target's first generated token, ``cache_lens`` [bsz] int32 = valid
         rows of every KV cache, ``prompt_bound`` = host-side bound of it.  Also the entry point of
-        synthetic-KV benchmarks, which fill the caches themselves instead of prefilling.  The eight keywords:
+        synthetic-KV benchmarks, which fill the caches themselves instead of prefilling.  The nine keywords:
         ``target_rules.py`` (``rules``: the ``TargetRules`` the caller has built from them already);
         ``prompt_ids[z, :cache_lens[z]]`` is the prompt the penalty state starts from (None: no prompt flags).  A round is the
         temperature-0 round with its Fn verification rows ruled inside the round and its graph: row j follows the committed
@@ -1067,7 +1067,7 @@ class LlamaGlide(LlamaForCausalLM):
         dev = first_token.device
         if rules is None:
             rules = self._rules(dev, temperature, self.model.layers[-1].self_attn.shard, head_sharded=True, sampling=sampling,
-                                penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark)
+                                penalties=penalties, logprobs=logprobs, stop=stop, ban=ban, guide=guide, dry=dry, watermark=watermark, cut=cut)
         bsz = first_token.shape[0]
         cand = [4, 16, 16, 16, 16] if tree_shape is None else list(tree_shape)
         acc_n = [1]

@@ -472,14 +472,18 @@ _sample_ws = _Workspace()    # its own buffer: a captured round holds its addres
 
 
 def sample_rows(logits: torch.Tensor, positions: torch.Tensor, sampling, streams: Optional[torch.Tensor] = None,
-                return_top2: bool = False, return_upper: bool = False):
+                return_top2: bool = False, return_upper: bool = False, cut=None):
     """One draw per row of lm_head outputs [..., V] from soft-max(x / T) under ``sampling``'s top-k / top-p
     (``ls_sample_rows``) and, where the object has them switched on, min_p / typical_p (``ls_sample_rows_ex``): int64 [...].  ``positions`` [...] int64 = absolute position of the token each row PREDICTS FROM
     (the position fed to RoPE for that row), ``streams`` [...] int32 = its batch row (None: 0) -- with the seed they key the
     noise, so a position draws the same noise in every loop.  ``return_top2``: also (top2_idx [..., 2], top2_key [..., 2],
     kept [...] int32, threshold [...] fp32 = the smallest kept value); ``return_upper`` appends upper [...] fp32, the largest
-    kept value (below the row maximum where typical_p dropped it)."""
+    kept value (below the row maximum where typical_p dropped it).  ``cut`` (``longspec_amd.Cut``, None: off): top_n_sigma and
+    xtc on the same draw (``ls_sample_rows_cut``; ``longspec_amd/cut.py`` has the definitions); a ``Cut`` with both filters off
+    is None."""
     _dev(logits, positions, streams)
+    if cut is not None and not (cut.top_n_sigma > 0.0 or cut.xtc_probability > 0.0):
+        cut = None
     min_p, typical_p = float(getattr(sampling, "min_p", 0.0)), float(getattr(sampling, "typical_p", 1.0))
     shape = logits.shape[:-1]
     V = logits.shape[-1]
@@ -505,7 +509,7 @@ def sample_rows(logits: torch.Tensor, positions: torch.Tensor, sampling, streams
         thr = torch.empty((n,), dtype=torch.float32, device=dev)
     lib = _C.load()
     ptr = lambda t: t.data_ptr() if t is not None else None
-    if min_p == 0.0 and typical_p == 1.0 and not return_upper:
+    if cut is None and min_p == 0.0 and typical_p == 1.0 and not return_upper:
         need = lib.ls_sample_workspace_bytes(n, V)
         ws = _sample_ws.get(dev, max(need, 1))
         _C.check(lib.ls_sample_rows(x.data_ptr(), n, V, x.stride(0), _dtype(x), pos.data_ptr(), ptr(strm), sampling.seed,
@@ -517,9 +521,16 @@ def sample_rows(logits: torch.Tensor, positions: torch.Tensor, sampling, streams
                           out_upper=ptr(upper), ld=x.stride(0), seed=sampling.seed, rows=n, vocab=V, dtype=_dtype(x),
                           top_k=sampling.top_k, temperature=sampling.temperature, top_p=sampling.top_p, min_p=min_p,
                           typical_p=typical_p)
-        need = lib.ls_sample_ex_workspace_bytes(C.byref(d))
-        ws = _sample_ws.get(dev, max(need, 1))
-        _C.check(lib.ls_sample_rows_ex(C.byref(d), ws.data_ptr(), ws.numel(), _stream()), "ls_sample_rows_ex")
+        if cut is None:
+            need = lib.ls_sample_ex_workspace_bytes(C.byref(d))
+            ws = _sample_ws.get(dev, max(need, 1))
+            _C.check(lib.ls_sample_rows_ex(C.byref(d), ws.data_ptr(), ws.numel(), _stream()), "ls_sample_rows_ex")
+        else:
+            c = _C.SampleCut(top_n_sigma=cut.top_n_sigma, xtc_probability=cut.xtc_probability, xtc_threshold=cut.xtc_threshold,
+                             reserved=0)
+            need = lib.ls_sample_cut_workspace_bytes(C.byref(d), C.byref(c))
+            ws = _sample_ws.get(dev, max(need, 1))
+            _C.check(lib.ls_sample_rows_cut(C.byref(d), C.byref(c), ws.data_ptr(), ws.numel(), _stream()), "ls_sample_rows_cut")
     res = (out.view(shape),)
     if return_top2:
         res += (t2i.view(*shape, 2), t2k.view(*shape, 2), kept.view(shape), thr.view(shape))

@@ -1,12 +1,12 @@
 """The rules on the TARGET's logits, in one place: what ``sampling=``, ``penalties=``, ``logprobs=``, ``stop=``, ``ban=``,
-``guide=``, ``dry=`` and ``watermark=`` of the generate loops and the ``begin_*_decode`` entry points (``llama_glide.py``) do to a
+``guide=``, ``dry=``, ``watermark=`` and ``cut=`` of the generate loops and the ``begin_*_decode`` entry points (``llama_glide.py``) do to a
 row of target logits, and
 the state they keep.  The loops build one ``TargetRules`` before any prefill and call it instead of spelling the operators out;
 a new rule is added here and nowhere else.  The draft passes are never ruled: the drafter stays greedy, unpenalised, unbanned
 and unguided (no DRY penalty and no watermark either), so a rule changes the acceptance length, never what the target accepts.
 
 The keywords (each: the argument, else -- where no ``temperature`` is given or it is 0 -- the process-wide default
-LONGSPEC_SAMPLING / _PENALTIES / _LOGPROBS / _STOP / _BAN / _GUIDE / _DRY / _WATERMARK, else off; all refused at ``temperature > 0``, the
+LONGSPEC_SAMPLING / _PENALTIES / _LOGPROBS / _STOP / _BAN / _GUIDE / _DRY / _WATERMARK / _CUT, else off; all refused at ``temperature > 0``, the
 reference's own T > 0 path):
 
 * ``sampling`` (``sampling.py``): every token of the target is one draw from its filtered distribution instead of the arg-max,
@@ -32,6 +32,8 @@ reference's own T > 0 path):
   the capture's shapes) to the largest pass seen.
 * ``watermark`` (``watermark.py``): every id that a keyed hash of the last ``context`` tokens of the text so far plus the row's
   draft tokens calls green gains ``delta``; a row with fewer tokens than that keeps its bits.  No state beyond the text.
+* ``cut`` (``cut.py``): top_n_sigma and xtc, two more filters on the draw of ``sampling`` -- refused without one, and where
+  ``sampling`` is.  No state; the log-probs stay those of the full ruled vocabulary.
 * ``logprobs`` (``logprobs.py``): the log-prob of every emitted token under the ruled distribution it was taken from and its
   top-n alternatives, in ``token`` [bsz, W] / ``top_ids`` / ``top`` [bsz, W, top_n], column for column with ``output_ids``.
 
@@ -53,6 +55,7 @@ from types import SimpleNamespace
 import torch
 
 from .ban import resolve as _resolve_ban
+from .cut import resolve as _resolve_cut
 from .dry import resolve as _resolve_dry
 from .guide import resolve as _resolve_guide
 from .logprobs import new_buffers as _logprob_buffers, resolve as _resolve_logprobs
@@ -68,7 +71,7 @@ class TargetRules:
     the shard's ``head_select`` (the tree loop), so ``sampling`` is refused under a vocabulary-parallel shard too."""
 
     def __init__(self, ops, vocab: int, device, temperature=None, shard=None, head_sharded=False, sampling=None, penalties=None,
-                 logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None):
+                 logprobs=None, stop=None, ban=None, guide=None, dry=None, watermark=None, cut=None):
         self.ops, self.vocab, self.device = ops, vocab, device
         self.sampling = _resolve_sampling(sampling, temperature, use_env=True)
         self.penalties = _resolve_penalties(penalties, temperature, use_env=True)
@@ -78,11 +81,13 @@ class TargetRules:
         guide = _resolve_guide(guide, temperature, use_env=True)
         dry = _resolve_dry(dry, temperature, use_env=True)
         watermark = _resolve_watermark(watermark, temperature, use_env=True)
+        self.cut = _resolve_cut(cut, temperature, use_env=True, sampling=self.sampling)     # None unless a filter is on
         if shard is not None and shard.vocab_parallel:
             for name, on in (("stop= with min_tokens > 0", stop is not None and stop.min_tokens > 0),
                              ("sampling=", head_sharded and self.sampling is not None), ("penalties=", self.penalties is not None),
                              ("logprobs=", lpc is not None), ("ban=", ban is not None), ("guide=", guide is not None),
-                             ("dry=", dry is not None), ("watermark=", watermark is not None)):
+                             ("dry=", dry is not None), ("watermark=", watermark is not None),
+                             ("cut=", head_sharded and self.cut is not None)):
                 if on:
                     raise ValueError(f"{name} is not available with a vocabulary-parallel shard")
         # (the tables check the ids, and nothing is copied to the device inside a graph capture)
@@ -144,7 +149,7 @@ class TargetRules:
         """Attach to the decode state ``st`` (``st.output_ids`` with the first token in place, and ``st.spec_mask`` where the
         loop has one, exist): sets ``st.rules`` and the attributes callers read -- ``sampling``, ``penalties``,
         ``token_state``, ``bias_table``, ``logprobs``, ``stop``, ``stop_state``, ``last_stop``, ``stopped``, ``ban``,
-        ``guide``, ``dry``, ``watermark`` --, counts ``first_token`` [bsz] into the penalty and guide states, writes ``first_logprobs``
+        ``guide``, ``dry``, ``watermark``, ``cut`` --, counts ``first_token`` [bsz] into the penalty and guide states, writes ``first_logprobs``
         to column 0
         (None, a caller that starts from synthetic caches: column 0 keeps the fill) and tests column 0 against the stops (a
         hit ends the loop with its first round, without a host read here).  ``where``: see the module; ``gamma``: the draft
@@ -172,7 +177,7 @@ class TargetRules:
             self.last_stop = _stop_result(self.stop_state)
         st.rules, st.stopped = self, False
         for name in ("sampling", "penalties", "token_state", "bias_table", "logprobs", "stop", "stop_state", "last_stop", "ban",
-                     "guide", "dry", "watermark"):
+                     "guide", "dry", "watermark", "cut"):
             setattr(st, name, getattr(self, name))
         self.advance(first_token.to(device=dev, dtype=torch.int64).view(bsz, 1))
 
@@ -210,14 +215,17 @@ class TargetRules:
 
     def tokens(self, logits, positions):
         """The target's token for every row of ``logits`` [bsz, (R,) V]: the arg-max, or with ``sampling`` one draw per row
-        keyed by ``positions`` -- the positions RoPE saw for those rows -- and the batch row."""
+        keyed by ``positions`` -- the positions RoPE saw for those rows -- and the batch row, under ``cut`` where one is on (the
+        keyword is passed only then)."""
         if self.sampling is None:
             return self.ops.argmax_rows(logits)
         streams = self.streams
         if logits.dim() == 3:
             bsz = logits.size(0)
             streams = streams.view(bsz, 1).expand(bsz, logits.size(1)) if bsz > 1 else None
-        return self.ops.sample_rows(logits, positions, self.sampling, streams=streams)
+        if self.cut is None:
+            return self.ops.sample_rows(logits, positions, self.sampling, streams=streams)
+        return self.ops.sample_rows(logits, positions, self.sampling, streams=streams, cut=self.cut)
 
     def pending(self, logits, tokens):
         """None without ``logprobs``; else the log-prob rows of ``tokens`` under the ruled ``logits`` they were taken from,

@@ -5,9 +5,11 @@ temperature > 0 round alternate, all replayed from HIP graphs, on the synthetic-
 
     python tools/ab_sampled_round.py [--blocks 6] [--per 15] [--sampling t=0.6,k=50,p=0.95,seed=1]
                                      [--more t=0.6,m=0.05,seed=1 --more t=0.6,typ=0.9,seed=1]
+                                     [--more "t=0.6,k=50,p=0.95,seed=1;sigma=1.0,xtcp=0.5,xtct=0.1"]
 
 ``--more SPEC`` adds a further sampled arm (named ``sampled[SPEC]``) to the interleaving: the min_p and typical_p rounds are
-held against the ``sampled`` arm (top-k / top-p, the launches of ``ls_sample_rows``) of the same run.
+held against the ``sampled`` arm (top-k / top-p, the launches of ``ls_sample_rows``) of the same run.  ``SPEC;CUT`` adds a
+LONGSPEC_CUT string (``cut=``: top_n_sigma, xtc) to the arm.
 
 Each figure is a host clock around `per` rounds that end in a device synchronise; the spread is what the blocks of ONE arm
 differ by on this box in this run, the yardstick for the difference between the arms.  The three arms keep their own decode
@@ -24,7 +26,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from longspec_amd import Sampling  # noqa: E402
+from longspec_amd import Cut, Sampling  # noqa: E402
 
 PREFIX, TEMPERATURE = 16384, 0.8
 ARMS = ("greedy", "sampled", "stochastic")
@@ -35,7 +37,8 @@ def main():
     ap.add_argument("--blocks", type=int, default=6)
     ap.add_argument("--per", type=int, default=15)
     ap.add_argument("--sampling", default="t=0.6,k=50,p=0.95,seed=1")
-    ap.add_argument("--more", action="append", default=[], help="a further sampled arm, a LONGSPEC_SAMPLING string")
+    ap.add_argument("--more", action="append", default=[],
+                    help="a further sampled arm, a LONGSPEC_SAMPLING string, optionally ';' and a LONGSPEC_CUT string")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sampled_round_ab.json"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "a measurement needs the GPU"
@@ -54,7 +57,8 @@ def main():
     first = torch.tensor([1000], dtype=torch.int64, device=dev)
     random.seed(99)
     torch.manual_seed(99)
-    more = {f"sampled[{spec}]": Sampling.parse(spec) for spec in args.more}
+    more = {f"sampled[{spec}]": (Sampling.parse(spec.partition(";")[0]), Cut.parse(spec.partition(";")[2]) if ";" in spec else None)
+            for spec in args.more}
     arms = ARMS + tuple(more)
     t = {a: [] for a in arms}
 
@@ -73,8 +77,8 @@ def main():
         states = {"greedy": m.begin_tree_decode(first, lens, PREFIX, bench.TREE, max_gen, eos_id=-1),
                   "sampled": m.begin_tree_decode(first, lens, PREFIX, bench.TREE, max_gen, eos_id=-1, sampling=sampling),
                   "stochastic": m.begin_tree_decode(first, lens, PREFIX, bench.TREE, max_gen, eos_id=-1, temperature=TEMPERATURE)}
-        for arm, s in more.items():
-            states[arm] = m.begin_tree_decode(first, lens, PREFIX, bench.TREE, max_gen, eos_id=-1, sampling=s)
+        for arm, (s, c) in more.items():
+            states[arm] = m.begin_tree_decode(first, lens, PREFIX, bench.TREE, max_gen, eos_id=-1, sampling=s, cut=c)
         assert states["greedy"].sampling is None, "unset LONGSPEC_SAMPLING: the greedy arm must be greedy"
         for arm, st in states.items():                 # every shape an arm uses, and the captures, before the clock
             st.eos = None
